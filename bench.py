@@ -13,10 +13,16 @@ format) the same way, for the records in DESIGN.md; the headline is config 2.
 --workload 5 is config 5: a mixed-format corpus (40 % 'combined', 30 % config-4
 NGINX, 30 % 'common' lines) parsed by one three-format handle (sticky active
 format on the device), streamed through it in ~1 GiB newline-aligned batches
-so the routing state is carried across batches; it also reports the
-PCIe-inclusive rate of host-resident batches (H2D copy inside the call).
+so the routing state is carried across batches; with --full it also reports
+the PCIe-inclusive rate of host-resident batches (H2D copy inside the call).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--lines L] [--workload 2|3|4|5]
+A plain run generates the input, warms up, times the steps and prints the
+result line.  --full adds the untimed legs after the steps (run histograms,
+the PCIe-inclusive rate, result delivery, PMC roofline traffic, the CPU
+baseline on the host cores).  --dump-outputs DIR writes a fixed sample of the
+last timed step's results as DIR/<name>.npy (dump_outputs).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--lines L] [--workload 2|3|4|5] [--full] [--dump-outputs DIR]
 """
 import argparse
 import concurrent.futures as cf
@@ -42,46 +48,77 @@ def log(*a):
 
 
 def generate_to_device(lpa, torch, workload, first_line, n_lines, device, chunk=1 << 20, workers=16, batch_bytes=0,
-                       front=0):
+                       front=0, piece=1 << 16):
     """Deterministic synthetic lines [first_line, first_line+n_lines) straight
-    into one HBM buffer at offset `front` (host generation in parallel chunks,
-    H2D in order).  With batch_bytes, consecutive chunks are grouped into
+    into one HBM buffer at offset `front` (host generation in parallel, H2D in
+    order).  Each chunk is generated in pieces of `piece` lines: lp_synth
+    writes a piece into a pinned staging buffer on a worker thread (no Python
+    copy of the bytes, the GIL released for the call) and the piece is copied
+    H2D asynchronously.  With batch_bytes, consecutive chunks are grouped into
     batches of about that size, each starting 4 KiB-aligned (as a streaming
     reader's staging buffers would).  Returns (buffer, bytes of lines,
     [(offset, bytes)] batches)."""
+    import ctypes
+    L = lpa.lib()
     upper = front + n_lines * 320 + (1 << 20)
     dev = torch.empty(upper, dtype=torch.uint8, device=device)
     pos = front
     batches = []
     bstart = front
-    starts = list(range(first_line, first_line + n_lines, chunk))
+    end_line = first_line + n_lines
+    jobs = []  # (first line, lines, starts a chunk)
+    for c in range(first_line, end_line, chunk):
+        for s in range(c, min(c + chunk, end_line), piece):
+            jobs.append((s, min(piece, c + chunk - s, end_line - s), s == c))
+    n_chunks = (n_lines + chunk - 1) // chunk
+    window = 2 * workers
+    cap = piece * 512 + (1 << 16)
+    stage = torch.empty((min(len(jobs), window + 2), cap), dtype=torch.uint8, pin_memory=True)
+    free = list(range(stage.shape[0]))
+    copying = []  # (slot, event of its H2D copy), oldest first
+
+    def gen(slot, s, n):
+        got = ctypes.c_int64(0)
+        nb = L.lp_synth(workload, SEEDS[workload], s, n, ctypes.c_void_p(stage[slot].data_ptr()), cap, ctypes.byref(got))
+        if nb < 0 or got.value != n:
+            raise RuntimeError("lp_synth: %d of %d lines from line %d in %d bytes" % (got.value, n, s, cap))
+        return slot, nb
+
+    def submit(ex, job):
+        if free:
+            slot = free.pop()
+        else:
+            slot, ev = copying.pop(0)
+            ev.synchronize()
+        return ex.submit(gen, slot, job[0], job[1])
+
     with cf.ThreadPoolExecutor(max_workers=workers) as ex:
         futs = []
         nxt = 0
-        window = 2 * workers
-        while nxt < len(starts) and len(futs) < window:
-            s = starts[nxt]
-            futs.append(ex.submit(lpa.synth, workload, SEEDS[workload], s, min(chunk, first_line + n_lines - s)))
+        while nxt < len(jobs) and len(futs) < window:
+            futs.append(submit(ex, jobs[nxt]))
             nxt += 1
         done = 0
         t0 = time.time()
-        while futs:
-            data = futs.pop(0).result()
-            if nxt < len(starts):
-                s = starts[nxt]
-                futs.append(ex.submit(lpa.synth, workload, SEEDS[workload], s, min(chunk, first_line + n_lines - s)))
-                nxt += 1
-            if batch_bytes and pos - bstart >= batch_bytes:
-                batches.append((bstart, pos - bstart))
-                pos = bstart = (pos + 4095) & ~4095
-            if pos + len(data) > upper:
+        for job in jobs:
+            slot, nb = futs.pop(0).result()
+            if job[2]:
+                if batch_bytes and pos - bstart >= batch_bytes:
+                    batches.append((bstart, pos - bstart))
+                    pos = bstart = (pos + 4095) & ~4095
+                done += 1
+                if done % 16 == 0:
+                    log("  generating chunk %d/%d (%.1f GB, %.0f s)" % (done, n_chunks, pos / 1e9, time.time() - t0))
+            if pos + nb > upper:
                 raise RuntimeError("synthetic data larger than the device buffer bound")
-            host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
-            dev[pos:pos + len(data)].copy_(host)
-            pos += len(data)
-            done += 1
-            if done % 16 == 0:
-                log("  generated %d/%d chunks (%.1f GB, %.0f s)" % (done, len(starts), pos / 1e9, time.time() - t0))
+            dev[pos:pos + nb].copy_(stage[slot, :nb], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            copying.append((slot, ev))
+            pos += nb
+            if nxt < len(jobs):
+                futs.append(submit(ex, jobs[nxt]))
+                nxt += 1
     torch.cuda.synchronize()
     batches.append((bstart, pos - bstart))
     return dev, sum(b[1] for b in batches), batches
@@ -390,6 +427,89 @@ def host_delivery(lpa, torch, parser, n_lines, workload, sample=100000):
     return out
 
 
+DUMP_LINES = 16384  # lines of the --dump-outputs sample (about 25 MB of .npy with all 123 paths)
+DUMP_SEED = 20261019
+
+
+class DeviceBytes:
+    """rows x width bytes at a device address, for torch.as_tensor"""
+
+    def __init__(self, ptr, rows, width):
+        self.__cuda_array_interface__ = {"shape": (rows, width), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+def dump_outputs(lpa, torch, parser, out_dir):
+    """--dump-outputs: what the last lp_parse_batch left for the caller (the
+    lp_result_view of the handle), as DIR/<name>.npy in float32 / float64, for
+    comparing two builds output for output.  A fixed sample of DUMP_LINES
+    lines (seeded, sorted; every line of a smaller batch):
+      counters              lines, ok, bad, fallback of the batch
+      lines                 the sampled line numbers
+      line_off              their byte offsets in the input
+      col.<name>.<index>    their element of every SoA column (a u64 element
+                            as two columns: low and high 32 bits); arena_base
+                            is left out: the arena regions are handed out by
+                            atomics, in scheduling order
+      table.<k>.<path>.*    the typed TABLE_COLS columns of the first
+                            DUMP_LINES lines (lp_result_table on the device
+                            view): valid, and values or (offsets, chars); the
+                            strings the refs and the arena resolve to"""
+    import ctypes
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    r = lpa.BatchResult(parser)
+    res = lpa.LpResult()
+    if lpa.lib().lp_result_view(parser._h, ctypes.byref(res)) != lpa.LP_OK:
+        raise RuntimeError("lp_result_view failed")
+    n = int(res.n_lines)
+    k = min(n, DUMP_LINES)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    dev = torch.device("cuda", parser.device)
+    sel = torch.from_numpy(idx).to(dev)
+    dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+    def gather(ptr, rows, width):
+        """the sampled rows of a device array of `rows` elements of `width` bytes"""
+        rows_u8 = torch.as_tensor(DeviceBytes(ptr, rows, width), device=dev).index_select(0, sel)
+        return rows_u8.cpu().numpy().view(dt[width]).reshape(-1)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, "".join(c if c.isalnum() or c in "._-" else "_" for c in name) + ".npy"), a)
+
+    def halves(a):
+        return np.stack([(a & 0xFFFFFFFF).astype(np.float64), (a >> 32).astype(np.float64)], axis=1)
+
+    save("counters", np.array([r.counters[c] for c in ("lines", "ok", "bad", "fallback")], dtype=np.float64))
+    if n == 0:
+        return
+    save("lines", idx.astype(np.float64))
+    save("line_off", gather(res.line_off, n + 1, 8).astype(np.float64))
+    status = r.status[idx]
+    save("status", status.astype(np.float32))
+    for j in range(res.n_columns):
+        c = res.column[j]
+        name = c.name.decode()
+        if name == "arena_base":
+            continue
+        a = gather(res.columns + c.offset, n, c.elem_size)
+        if name != "status":
+            a[status != lpa.LINE_OK] = 0  # a line that is not OK has no values
+        a = halves(a) if c.elem_size == 8 else a.astype(np.float32 if c.elem_size < 4 else np.float64)
+        save("col.%s.%d" % (name, c.index), a)
+    cols = [c for c in TABLE_COLS if c[0] in parser.fields]
+    if cols:
+        t = r.table_device(cols, first=0, count=k)
+        for j, (path, typ) in enumerate(cols):
+            vals, valid = t[path]
+            save("table.%d.%s.valid" % (j, path), valid.cpu().numpy().astype(np.float32))
+            if typ is str:
+                save("table.%d.%s.offsets" % (j, path), vals[0].cpu().numpy().astype(np.float64))
+                save("table.%d.%s.chars" % (j, path), vals[1].cpu().numpy().astype(np.float32))
+            else:
+                save("table.%d.%s.values" % (j, path), vals.cpu().numpy().astype(np.float64))
+    log("outputs of the last step written to %s" % out_dir)
+
+
 def pmc_traffic(path, n_lines, lib_path, kernel="k_parse_chunks"):
     """HBM bytes per launch of `kernel` measured by PMC counters, or None."""
     try:
@@ -441,9 +561,16 @@ def main():
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_traffic_latest.json"),
                     help="tools/pmc_traffic.py summary of separate rocprofv3 --pmc passes; fills roofline.traffic "
                          "when it was taken on this workload with this exact engine build")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed legs: run histograms, PCIe-inclusive rate "
+                         "(--workload 5), result delivery, PMC roofline traffic, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left in the handle as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the first action, before torch or any GPU call: N rank processes
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -573,7 +700,9 @@ def main():
     pk_bytes, uk_bytes = stats["bytes_parse_kernels"], stats["bytes_uri_kernels"]
     achieved = pk_bytes / (avg_pk / 1e3) / 1e9
     uri_gbs = uk_bytes / (avg_uk / 1e3) / 1e9 if avg_uk > 0 else 0.0
-    with_pmc = wl == 2 and args.fields == "all"
+    if args.dump_outputs and rank == 0:  # before any untimed leg parses another batch with the handle
+        dump_outputs(lpa, torch, parser, args.dump_outputs)
+    with_pmc = args.full and wl == 2 and args.fields == "all"
     # the dominant kernel: the one-pass chunked parse (several LogFormats: its
     # routing instance, k_parse_chunks<.., MF>, since round 6)
     pk_name = "k_parse_chunks" if len(fmt.split("\n")) == 1 else "k_parse_chunks (several LogFormats: routing instance)"
@@ -646,9 +775,28 @@ def main():
             },
         },
         "cpu_baseline": None,
+        "full": args.full,
     }
+    if wl == 5:
+        result["config"]["formats"] = fmt.split("\n")
+        result["config"]["corpus_bytes_all_ranks"] = total_bytes
+    if world > 1:
+        result["status_counts_all_ranks"] = {k: int(counters[j]) for j, k in enumerate(("lines", "ok", "bad", "fallback"))}
+    if args.full:
+        full_legs(args, lpa, torch, parser, result, buf, batches, stats, fields, device, rank, world)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_legs(args, lpa, torch, parser, result, buf, batches, stats, fields, device, rank, world):
+    """--full: what the benchmark measures besides its headline figure, after
+    (and outside) the timed steps; every rank calls it (the histograms are
+    all-reduced)."""
+    from logparser_amd.shard import reduce_counters
+    wl = args.workload
     # run histograms of the last step's batch (device kernel), all-reduced over the ranks
-    # (outside the timed region)
     hist = torch.zeros(lpa.HIST_WORDS, dtype=torch.int64, device=device)
     if len(batches) == 1:
         parser.histograms(device_ptr=hist.data_ptr())
@@ -658,13 +806,8 @@ def main():
         result["histograms"] = {"lines": hd["lines"], "ok": hd["ok"], "bad": hd["bad"], "fallback": hd["fallback"],
                                 "status_top": {str(c): v for c, v in top}, "methods": hd["methods"],
                                 "note": "lp_histograms of the last step (all ranks, RCCL all-reduce), untimed"}
-    if wl == 5:
-        result["config"]["formats"] = fmt.split("\n")
-        result["config"]["corpus_bytes_all_ranks"] = total_bytes
-        if rank == 0:
-            result["pcie_inclusive"] = pcie_inclusive(torch, parser, buf, batches, 8 << 30)
-    if world > 1:
-        result["status_counts_all_ranks"] = {k: int(counters[j]) for j, k in enumerate(("lines", "ok", "bad", "fallback"))}
+    if wl == 5 and rank == 0:
+        result["pcie_inclusive"] = pcie_inclusive(torch, parser, buf, batches, 8 << 30)
     if rank == 0 and wl != 5 and not args.no_delivery:
         result["delivery"] = host_delivery(lpa, torch, parser, stats["lines"], wl)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -672,10 +815,6 @@ def main():
         result["cpu_baseline"] = cpu_baseline(lpa, wl, fields, args.cpu_sample_lines, args.cpu_threads)
         # vs_baseline stays null: BASELINE.md publishes no number for this metric
         result["vs_cpu_baseline"] = round(result["value"] / result["cpu_baseline"]["value"], 1)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
