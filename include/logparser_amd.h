@@ -179,8 +179,13 @@ int64_t lp_line_record_json(lp_handle *h, int64_t i, char *out, size_t cap);
  * out[7] = waves whose URI bytes exceeded the URI kernel's compact buffer
  * (their URI stages read the input from HBM directly), out[8] = one-format
  * programs: byte chunks redone by the deferred pass (their wave stopped
- * waiting for its first line number; 0 normally, see LP_OPT_CHUNK_WAIT).
- * Returns the words written (at most 9). */
+ * waiting for its first line number; 0 normally, see LP_OPT_CHUNK_WAIT),
+ * out[9] = lines the chunk kernel queued for the overflow kernels because
+ * the first leaf of the match did not decide them (they need the backtracking
+ * DFS, or the routing of a several-format program does); lines queued
+ * because their chunk's window does not hold them, or as a chunk's 65th line
+ * onwards, are not counted.
+ * Returns the words written (at most 10). */
 int lp_counters(lp_handle *h, uint64_t *out, int n);
 
 /* Device-side timing of the last batch, in milliseconds, measured with HIP

@@ -113,6 +113,7 @@ struct lp_handle {
     uint64_t ovf_waves = 0;        // waves of the last batch parsed by k_parse_overflow (chunked: lines by k_parse_ovf_lines)
     uint64_t uri_ovf_waves = 0;    // ... whose URI stages ran in k_uri_overflow
     uint64_t deferred = 0;         // chunks of the last batch parsed by the deferred pass (normally 0)
+    uint64_t dfs_lines = 0;        // lines of the last batch the chunk kernel queued for the backtracking DFS
     uint64_t shard_top[LP_ARENA_SHARDS]{};
     lp::ParseLaunch last_launch{};  // the last enqueue's launch parameters (diagnostics)
     uint64_t arena_written = 0;
@@ -503,6 +504,7 @@ int finish(lp_handle* h) {
             h->ovf_waves = h->chunked ? m.ovf_lines : m.ovf_waves;
             h->uri_ovf_waves = m.uri_ovf_waves;
             h->deferred = h->chunked ? m.deferred : 0;
+            h->dfs_lines = h->chunked ? m.dfs_lines : 0;
         } else {
             h->counters[0] = (uint64_t)n;
             h->counters[1] = h->counters[2] = 0;
@@ -836,10 +838,10 @@ int lp_counters(lp_handle* h, uint64_t* out, int n) {
     if (!h || !out) return LP_E_INVALID;
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
-    const uint64_t v[9] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
-                           (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred};
-    for (int k = 0; k < n && k < 9; ++k) out[k] = v[k];
-    return n < 9 ? n : 9;
+    const uint64_t v[10] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
+                            (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines};
+    for (int k = 0; k < n && k < 10; ++k) out[k] = v[k];
+    return n < 10 ? n : 10;
 }
 
 int lp_histograms(lp_handle* h, uint64_t* out, int out_on_device) {

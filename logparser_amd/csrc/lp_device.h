@@ -987,6 +987,120 @@ __host__ __device__ LP_INLINE int uplist_ns_end(const Program& P, const ElemV& e
     return found;
 }
 
+// The candidate ends of an IP token.  FORMAT_IP (TokenParser.java:43-52) is
+// IPv4 | IPv6, FORMAT_CLF_IP adds '-'.  Every IPv4 end is also an end of the
+// IPv6 branch ":?(?:H{1,4}(?::|.)?){0,8}(?::|::)?(?:H{1,4}(?::|.)?){0,8}"
+// (digits are hex, '.' matches the dots), so the reachable ends of that
+// branch, simulated as bit sets over the bytes it can span, are all of the
+// token's ends but CLF's '-'.  An end counts when the rest of the format can
+// follow it (the element's next literal, or '$').
+// java.util.regex keeps the first end, in its priority order, from which the
+// rest of the pattern matches, and the capture is the span (p, end) whatever
+// path led there.  So when exactly one distinct end lets the rest match it is
+// the result whatever the order: the order itself is never modelled.
+// 128-bit set in two registers (no arrays: dynamically indexed arrays go to
+// scratch memory on the GPU)
+struct Set128 {
+    uint64_t lo = 0, hi = 0;
+    __host__ __device__ LP_INLINE void add(int k) {
+        if (k < 64) lo |= 1ull << k;
+        else if (k < 128) hi |= 1ull << (k - 64);
+    }
+    __host__ __device__ LP_INLINE bool any() const { return (lo | hi) != 0; }
+    __host__ __device__ LP_INLINE int count() const { return popc64(lo) + popc64(hi); }
+    __host__ __device__ LP_INLINE int first() const {  // the smallest member (any())
+        return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(hi);
+    }
+    // f(k) for every member k, ascending (one copy of f's code)
+    template <typename F>
+    __host__ __device__ LP_INLINE void each(F&& f) const {
+        uint64_t a = lo, b = hi;
+        while (a | b) {
+            int k;
+            if (a) { k = __builtin_ctzll(a); a &= a - 1; }
+            else { k = 64 + __builtin_ctzll(b); b &= b - 1; }
+            f(k);
+        }
+    }
+};
+
+// Can the rest of the format follow an end of token e at q?
+template <typename LN>
+__host__ __device__ LP_INLINE bool tok_end_follows(const Program& P, const LN& L, const ElemV& e, int q) {
+    return e.last ? q == L.n : (!e.nlit || lit_at(P, L, q, e));
+}
+
+// ip_alt_ends: the ends of the IPv6 branch at p other than cur that the rest
+// of the format can follow, as a bit set (bit k = end p + k).  false: an end
+// lies beyond the set's range (separators of several UTF-8 bytes): the set
+// is incomplete and the caller must not decide from it.
+template <typename LN>
+__host__ __device__ LP_INLINE bool ip_alt_ends(const Program& P, const LN& L, const ElemV& e, int p, int cur,
+                                               Set128& ends) {
+    constexpr int W = 96;
+    bool whole = true;
+    auto hexat = [&](int q) {
+        if (q >= L.n) return false;
+        const uint32_t c = L[q];
+        return (c - '0' < 10u) || ((c | 32u) - 'a' < 6u);
+    };
+    Set128 cur_set;
+    cur_set.add(0);
+    if (p < L.n && L[p] == ':') cur_set.add(1);
+    // one (H{1,4}(?::|.)?) group from every position of m, up to 8 times
+    auto groups = [&](Set128 m, Set128& acc) {
+        for (int it = 0; it < 8; ++it) {
+            Set128 nx;
+            m.each([&](int k) {
+                for (int h = 1; h <= 4 && hexat(p + k + h - 1); ++h) {
+                    if (k + h < W) nx.add(k + h);
+                    else whole = false;
+                    if (p + k + h < L.n) {  // (?::|.): any char but a line terminator (1-4 UTF-8 bytes)
+                        const int cl = utf8_len(L[p + k + h]);
+                        if (k + h + cl < W) nx.add(k + h + cl);
+                        else whole = false;
+                    }
+                }
+            });
+            if (!nx.any()) break;
+            acc.lo |= nx.lo;
+            acc.hi |= nx.hi;
+            m = nx;
+        }
+    };
+    Set128 all = cur_set;
+    groups(cur_set, all);
+    Set128 mid = all;
+    all.each([&](int k) {
+        if (p + k >= L.n || L[p + k] != ':') return;
+        if (k + 1 < W) mid.add(k + 1);
+        else whole = false;
+        if (p + k + 1 < L.n && L[p + k + 1] == ':') {
+            if (k + 2 < W) mid.add(k + 2);
+            else whole = false;
+        }
+    });
+    Set128 fin = mid;
+    groups(mid, fin);
+    ends = Set128{};
+    fin.each([&](int k) {
+        if (p + k == cur || p + k > L.n) return;
+        if (tok_end_follows(P, L, e, p + k)) ends.add(k);
+    });
+    return whole;
+}
+
+// ip_end_set: the whole candidate set of the IP token e at p other than cur
+// (the IPv4 ends and the IPv6 branch's: ip_alt_ends; FORMAT_CLF_IP's '-').
+// false: incomplete (ip_alt_ends).
+template <typename LN>
+__host__ __device__ LP_INLINE bool ip_end_set(const Program& P, const LN& L, const ElemV& e, int p, int cur,
+                                              Set128& ends) {
+    const bool whole = ip_alt_ends(P, L, e, p, cur, ends);
+    if (e.kind == EK_CLF_IP && p < L.n && L[p] == '-' && p + 1 != cur && tok_end_follows(P, L, e, p + 1)) ends.add(1);
+    return whole;
+}
+
 // First candidate end of element e at position p (exact leftmost-first
 // order), -1 = none, -2 = FALLBACK.  '.' runs to the end of the line: the
 // fast-path guard already rejected every line terminator.
@@ -1045,7 +1159,7 @@ __host__ __device__ LP_INLINE int cand_first(const Program& P, const ElemV& e, c
         // IPv6 alternative can only match empty at '-' (no hex/':'), so '-'
         // is exact when the following literal cannot start at p.
         if (e.kind == EK_CLF_IP && p < L.n && L[p] == '-' && e.nlit && (e.lit4 & 0xFFu) != '-') return p + 1;
-        return -2;  // resolved by match_line (ip_resolve)
+        return -2;  // no dotted quad: resolved by match_line (ip_resolve)
     }
     case EK_ANYCHAR: if constexpr (SIMPLE) return -2; else return p < L.n ? p + utf8_len(L[p]) : -1;  // '.': one char (the guard rejected line terminators)
     case EK_DECIMAL: if constexpr (SIMPLE) return -2; else return decimal_at(L, p);
@@ -1108,87 +1222,6 @@ __host__ __device__ LP_INLINE int cand_first(const Program& P, const ElemV& e, c
     return -2;
 }
 
-// Could another alternative of FORMAT_IP (TokenParser.java:43-51) at p end
-// somewhere other than cur and be followed by the rest of the format (its
-// next literal, or '$')?  Every IPv4 end is also an end of the IPv6 branch
-// ":?(?:H{1,4}(?::|.)?){0,8}(?::|::)?(?:H{1,4}(?::|.)?){0,8}" (digits are
-// hex, '.' matches the dots), so the reachable ends of that branch are
-// simulated as bit sets over the <= 83 bytes it can span.
-// ip_alt_ends: the same ends as a bit set (bit k = end p + k); returns
-// whether there is any.
-// 128-bit set in two registers (no arrays: dynamically indexed arrays go to
-// scratch memory on the GPU)
-struct Set128 {
-    uint64_t lo = 0, hi = 0;
-    __host__ __device__ LP_INLINE void add(int k) {
-        if (k < 64) lo |= 1ull << k;
-        else if (k < 128) hi |= 1ull << (k - 64);
-    }
-    __host__ __device__ LP_INLINE bool any() const { return (lo | hi) != 0; }
-    // f(k) for every member k, ascending
-    template <typename F>
-    __host__ __device__ LP_INLINE void each(F&& f) const {
-        for (uint64_t m = lo; m; m &= m - 1) f(__builtin_ctzll(m));
-        for (uint64_t m = hi; m; m &= m - 1) f(64 + __builtin_ctzll(m));
-    }
-};
-
-template <typename LN>
-__host__ __device__ LP_INLINE bool ip_alt_ends(const Program& P, const LN& L, const ElemV& e, int p, int cur,
-                                               Set128& ends) {
-    constexpr int W = 96;
-    auto hexat = [&](int q) {
-        if (q >= L.n) return false;
-        const uint32_t c = L[q];
-        return (c - '0' < 10u) || ((c | 32u) - 'a' < 6u);
-    };
-    Set128 cur_set;
-    cur_set.add(0);
-    if (p < L.n && L[p] == ':') cur_set.add(1);
-    // one (H{1,4}(?::|.)?) group from every position of m, up to 8 times
-    auto groups = [&](Set128 m, Set128& acc) {
-        for (int it = 0; it < 8; ++it) {
-            Set128 nx;
-            m.each([&](int k) {
-                for (int h = 1; h <= 4 && hexat(p + k + h - 1); ++h) {
-                    if (k + h < W) nx.add(k + h);
-                    if (p + k + h < L.n) {  // (?::|.): any char but a line terminator (1-4 UTF-8 bytes)
-                        const int cl = utf8_len(L[p + k + h]);
-                        if (k + h + cl < W) nx.add(k + h + cl);
-                    }
-                }
-            });
-            if (!nx.any()) break;
-            acc.lo |= nx.lo;
-            acc.hi |= nx.hi;
-            m = nx;
-        }
-    };
-    Set128 all = cur_set;
-    groups(cur_set, all);
-    Set128 mid = all;
-    all.each([&](int k) {
-        if (p + k >= L.n || L[p + k] != ':') return;
-        if (k + 1 < W) mid.add(k + 1);
-        if (p + k + 1 < L.n && L[p + k + 1] == ':' && k + 2 < W) mid.add(k + 2);
-    });
-    Set128 fin = mid;
-    groups(mid, fin);
-    bool any = false;
-    ends = Set128{};
-    fin.each([&](int k) {
-        if (p + k == cur || p + k > L.n) return;
-        if (e.last ? p + k == L.n : (!e.nlit || lit_at(P, L, p + k, e))) { ends.add(k); any = true; }
-    });
-    return any;
-}
-
-template <typename LN>
-__host__ __device__ LP_INLINE bool ip_alt_end_possible(const Program& P, const LN& L, const ElemV& e, int p, int cur) {
-    Set128 ends;
-    return ip_alt_ends(P, L, e, p, cur, ends);
-}
-
 // Next candidate after 'cur' (same priority order).  SIMPLE: see cand_first.
 template <bool SIMPLE = false, typename LN>
 __host__ __device__ LP_INLINE int cand_next(const Program& P, const ElemV& e, const LN& L, int p, int cur) {
@@ -1210,10 +1243,12 @@ __host__ __device__ LP_INLINE int cand_next(const Program& P, const ElemV& e, co
     case EK_TIME_US: return -1;
     case EK_CLF_IP: case EK_IP:
         if constexpr (SIMPLE) return -2;
-        if (L[p] == '-') return -1;
-        // shorter IPv4 / IPv6 alternatives: exact only when none of them can
-        // be followed by the rest of the format
-        return ip_alt_end_possible(P, L, e, p, cur) ? -2 : -1;
+        // no other member of the candidate set: exact; else match_line
+        // resolves them (ip_resolve)
+        {
+            Set128 ends;
+            return !ip_end_set(P, L, e, p, cur, ends) || ends.any() ? -2 : -1;
+        }
     case EK_ANYCHAR: case EK_MSEC: case EK_UPLIST_NS: case EK_BINIP: case EK_TIME_ISO: case EK_CACHE_STATUS:
         return -1;
     case EK_DECIMAL: {  // a shorter fraction
@@ -1250,36 +1285,52 @@ struct NoCapsDfs {
 // elems: the ne elements of one LogFormat.
 // elems: the program's element table (the kernel passes an LDS copy).
 //
-// An IP token whose other alternatives could end elsewhere (cand_* = -2:
-// the IPv6 branch of FORMAT_IP, TokenParser.java:43-52, and FORMAT_CLF_IP's
-// '-') is resolved exactly when none of those ends lets the rest of the
-// format match: a nested DFS over the remaining elements from each such end
-// (stack entries above the caller's; Nested = no further nesting).  Then the
-// token has no further candidate (-1); otherwise the line is FALLBACK, as
-// the priority order among the IPv6 branch's ends is not modelled.
+// An IP token with several candidate ends (cand_* = -2: the ends of
+// FORMAT_IP's IPv6 branch, TokenParser.java:43-52, the IPv4 ends and
+// FORMAT_CLF_IP's '-' that the next literal follows, ip_end_set) is resolved
+// by a nested DFS over the remaining elements from every such end (stack
+// entries above the caller's; Nested = no further nesting).  No end completes
+// the match: the token has no further candidate (-1).  Exactly one does: it
+// is the token's candidate whatever the priority order, and it has no
+// successor.  Two or more complete, or a nested run is undecided: the line
+// is FALLBACK, as the priority order among the ends is not modelled.
+// The nested runs count their steps in the line's one budget (psteps).
 template <bool Nested = false, bool SIMPLE = false, typename LN, typename EL, typename Caps, typename Stk>
 __host__ __device__ LP_INLINE int match_line(const Program& P, const EL& elems, int ne, const LN& L, Caps& caps,
-                                             Stk stk, int pos0 = 0, int sp0 = 0) {
+                                             Stk stk, int pos0 = 0, int sp0 = 0, int* psteps = nullptr) {
     int i = 0, pos = pos0, sp = sp0;
-    int steps = 0;
+    int own_steps = 0;
+    int& steps = Nested && psteps ? *psteps : own_steps;
     const int budget = 16 * L.n + 256;
-    // -1 when no alternative end of the IP element j at p (other than cur)
-    // completes the match, -2 otherwise
+    // the candidate of the IP element j at p after cur (-1: its first): -1
+    // none, -2 undecided
     auto ip_resolve = [&](int j, int p, int cur, int spn) -> int {
-        if constexpr (Nested || SIMPLE) {
+        if constexpr (SIMPLE) {
             return -2;
         } else {
             const ElemV e = load_elem(elems + j);
             if (e.kind != EK_IP && e.kind != EK_CLF_IP) return -2;
             Set128 ends;
-            ip_alt_ends(P, L, e, p, cur, ends);
-            if (e.kind == EK_CLF_IP && p < L.n && L[p] == '-' && p + 1 != cur) ends.add(1);  // the '-' alternative
-            NoCapsDfs nc;
-            bool hit = false;
-            ends.each([&](int k) {
-                if (!hit && match_line<true, SIMPLE>(P, elems + j + 1, ne - j - 1, L, nc, stk, p + k, spn) != ST_BAD) hit = true;
-            });
-            return hit ? -2 : -1;
+            if (!ip_end_set(P, L, e, p, cur, ends)) return -2;
+            if (!ends.any()) return -1;
+            // a sole end is the token's only candidate: no nested run (as the
+            // first candidate only: after cur the set leaves cur out, and cur's
+            // predecessors are in it)
+            if (cur < 0 && ends.count() == 1) return p + ends.first();
+            if constexpr (Nested) {
+                return -2;
+            } else {
+                NoCapsDfs nc;
+                int found = -1;
+                bool open = false;  // two completing ends, or an undecided run
+                ends.each([&](int k) {
+                    if (open) return;
+                    const int st = match_line<true, SIMPLE>(P, elems + j + 1, ne - j - 1, L, nc, stk, p + k, spn, &steps);
+                    if (st == ST_FALLBACK || (st == ST_OK && found >= 0)) open = true;
+                    else if (st == ST_OK) found = p + k;
+                });
+                return open ? -2 : found;
+            }
         }
     };
     for (;;) {

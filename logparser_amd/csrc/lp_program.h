@@ -65,8 +65,9 @@ enum ElemKind : uint8_t {
     EK_ANY_GREEDY,   // .*
     EK_ANY_LAZY,     // .*?
     EK_TIME_US,      // [0-3][0-9]/(?:[a-zA-Z]{3})/[1-9][0-9]{3}:[0-9]{2}:[0-9]{2}:[0-9]{2} [\+|\-][0-9]{4}
-    EK_CLF_IP,       // IPv4|IPv6|-  (IPv4 dotted quad or '-' on device, else FALLBACK)
-    EK_IP,           // IPv4|IPv6
+    EK_CLF_IP,       // IPv4|IPv6|-  (the dotted quad and '-' by the first leaf; other tokens, IPv6 addresses
+                     //               among them, by match_line: FALLBACK only when several ends complete the match)
+    EK_IP,           // IPv4|IPv6    (the same without '-')
     // NGINX token regexes (nginxmodules/CoreLogModule.java, UpstreamModule.java)
     EK_ANYCHAR,      // .                                  ($pipe)
     EK_DECIMAL,      // [0-9]+\.[0-9]+                      ($request_time, SECOND_MILLIS)
@@ -368,7 +369,8 @@ struct Meta {
     // lines): how many failed, and the first failure (kind, then four values;
     // see check_fail in parse.hip).  Non-zero fails the batch (LP_E_DEVICE).
     unsigned long long err;
-    unsigned long long err_info[15];  // (5 used; the rest keeps shard_top on its own 128-B lines)
+    unsigned long long err_info[14];  // (13 used; with dfs_lines it keeps shard_top on its own 128-B lines)
+    unsigned long long dfs_lines;    // lines the chunk kernel queued because the first leaf did not decide them (ST_REDO)
     unsigned long long shard_top[ARENA_SHARDS * 16];  // bump pointer of shard s at [16 s] (own 128-B line)
 };
 

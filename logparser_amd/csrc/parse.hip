@@ -432,6 +432,10 @@ __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uin
     const bool redo = lds_line && o.status == ST_REDO;
     const bool row = mine && lds_line && !redo;
     if (mine && (!lds_line || redo)) queue_line(C, (uint64_t)li);
+    {
+        const uint32_t nredo = (uint32_t)__popcll(__ballot(mine && redo));
+        if (nredo && lane == 0) atomicAdd(&C.meta->dfs_lines, (unsigned long long)nredo);
+    }
     if (row) {
         write_line(P, o, C, li);
         if (!P.has_phase2()) C.arena_base[li] = 0;  // no URI kernel: an empty region for every line
