@@ -184,8 +184,11 @@ int64_t lp_line_record_json(lp_handle *h, int64_t i, char *out, size_t cap);
  * the first leaf of the match did not decide them (they need the backtracking
  * DFS, or the routing of a several-format program does); lines queued
  * because their chunk's window does not hold them, or as a chunk's 65th line
- * onwards, are not counted.
- * Returns the words written (at most 10). */
+ * onwards, are not counted; out[10] = lines whose URI stages were redone
+ * with the repair on (a malformed URI that HttpUriDissector repairs before
+ * URI.create: bad '%' escapes, "&amp;" and numeric entities, "=#", "#&",
+ * several '#').
+ * Returns the words written (at most 11). */
 int lp_counters(lp_handle *h, uint64_t *out, int n);
 
 /* Device-side timing of the last batch, in milliseconds, measured with HIP

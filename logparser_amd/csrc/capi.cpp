@@ -114,6 +114,7 @@ struct lp_handle {
     uint64_t uri_ovf_waves = 0;    // ... whose URI stages ran in k_uri_overflow
     uint64_t deferred = 0;         // chunks of the last batch parsed by the deferred pass (normally 0)
     uint64_t dfs_lines = 0;        // lines of the last batch the chunk kernel queued for the backtracking DFS
+    uint64_t uri_fix_lines = 0;    // lines of the last batch whose URI stages were redone with the repair on (uri_redo_line)
     uint64_t shard_top[LP_ARENA_SHARDS]{};
     lp::ParseLaunch last_launch{};  // the last enqueue's launch parameters (diagnostics)
     uint64_t arena_written = 0;
@@ -375,10 +376,11 @@ int enqueue(lp_handle* h, bool sync_count) {
     C.cap_lines = cap;
     const int64_t waves = lp::parse_waves(cap);
     if (!h->waves.ensure(4 * lp::WC_WORDS * (size_t)(waves + 1))) return LP_E_NOMEM;
-    if (!h->ovf.ensure(8 * (size_t)(waves + 1))) return LP_E_NOMEM;
+    if (!h->ovf.ensure(8 * (size_t)(waves + 1) + 4 * (size_t)(cap + 1))) return LP_E_NOMEM;
     C.wave_counts = h->waves.as<uint32_t>();
     C.ovf_list = h->ovf.as<uint32_t>();
     C.uri_ovf_list = h->ovf.as<uint32_t>() + (waves + 1);
+    C.uri_fix_list = h->ovf.as<uint32_t>() + 2 * (waves + 1);  // one entry per line
     if (h->plan.device_ok()) {
         if (P.n_fmt > 1) {  // sticky multi-format routing scratch
             if (!h->route.ensure(8 * (size_t)(lp::fmt_chunks(cap) + 1))) return LP_E_NOMEM;
@@ -505,6 +507,7 @@ int finish(lp_handle* h) {
             h->uri_ovf_waves = m.uri_ovf_waves;
             h->deferred = h->chunked ? m.deferred : 0;
             h->dfs_lines = h->chunked ? m.dfs_lines : 0;
+            h->uri_fix_lines = (m.uri_fix_lines & 0xFFFFFFFFull) + (m.uri_fix_lines >> 32);  // the queued ones, k_uri_overflow's own
         } else {
             h->counters[0] = (uint64_t)n;
             h->counters[1] = h->counters[2] = 0;
@@ -838,10 +841,11 @@ int lp_counters(lp_handle* h, uint64_t* out, int n) {
     if (!h || !out) return LP_E_INVALID;
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
-    const uint64_t v[10] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
-                            (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines};
-    for (int k = 0; k < n && k < 10; ++k) out[k] = v[k];
-    return n < 10 ? n : 10;
+    const uint64_t v[11] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
+                            (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines,
+                            h->uri_fix_lines};
+    for (int k = 0; k < n && k < 11; ++k) out[k] = v[k];
+    return n < 11 ? n : 11;
 }
 
 int lp_histograms(lp_handle* h, uint64_t* out, int out_on_device) {
@@ -894,8 +898,12 @@ int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
     // URI kernels: the gathered URI bytes, per line the status, line start,
     // token flags and one source span per URI stage, their columns and arena
     const uint64_t parse_b = h->nbytes + 8 * (n1 + 1) + n1 * (row - 8 - row_uri);
+    // (a redone line, uri_redo_line: the line read again from HBM, a mean
+    // line's bytes, and its URI columns written again; its second region is
+    // in arena_written)
+    const uint64_t redo_b = h->uri_fix_lines * ((n1 ? h->nbytes / n1 : 0) + row_uri);
     const uint64_t uri_b = P.has_phase2() ? h->uri_src_bytes + n1 * (1 + 8 + 4 + 4 * (uint64_t)P.n_uri) + n1 * row_uri +
-                                         h->arena_written : 0;
+                                         h->arena_written + redo_b : 0;
     uint64_t v[4] = {h->nbytes, n1 * row + h->arena_written, parse_b, uri_b};
     for (int k = 0; k < n && k < 4; ++k) out[k] = v[k];
     return n < 4 ? n : 4;

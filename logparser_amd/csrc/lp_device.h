@@ -9,6 +9,9 @@
 //
 // Any input the device cannot prove it handles exactly returns FALLBACK
 // (status 2): the caller hands that line to the reference Java dissector.
+// (A malformed URI that the reference repairs before URI.create is not
+// among them: uri_repair restates that chain; what it leaves to FALLBACK is
+// listed there.)
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -19,8 +22,10 @@
 namespace lp {
 
 enum : int { ST_OK = 0, ST_BAD = 1, ST_FALLBACK = 2,
-             ST_REDO = 3 };  // (kernel-internal, never stored: the line needs the backtracking DFS, which
+             ST_REDO = 3,    // (kernel-internal, never stored: the line needs the backtracking DFS, which
                              // the one-pass chunk kernel leaves to the queued-line kernel; phase1<..., DFS = false>)
+             ST_REPAIR = 4 };  // (kernel-internal, never stored: a URI stage met a malformed URI that uri_repair
+                               // decides; the URI kernels store FALLBACK and have the line redone, uri.hip uri_redo_line)
 
 // Profiling build only (-DLP_PROFILE): wave timestamps at fixed points,
 // stored per wave (the waves of blocks [PROF_W0, PROF_W0 + PROF_WAVES)),
@@ -3429,12 +3434,23 @@ __host__ __device__ LP_INLINE void uri_walk_fast(const Program& P, int u, const 
     LP_PROF(51 + 4 * u);
 }
 
+// What a URI stage does with a malformed URI that the reference repairs
+// before URI.create (uri_repair below): UR_OFF returns the internal status
+// ST_REPAIR (the wave code of the URI kernels, which has the line redone), UR_ON repairs it
+// inline (the host build, uri_redo_line, k_derived_lines), UR_DONE runs
+// on a string uri_repair produced: what is left of such patterns is text.
+enum : int { UR_OFF = 0, UR_ON = 1, UR_DONE = 2 };
+template <typename LN, typename Cols>
+__host__ __device__ LP_INLINE int uri_repair(const Program& P, int u, const LN& L, int a, int b, Arena& R, Cols& C,
+                                             int64_t li);
+
 // HttpUriDissector on the line bytes [a,b) after the fast walk: the general
 // walk from Wk.resume, the query table's last piece, then the URI's parts.
 // Returns status.
-template <typename LN, typename Cols, typename UO>
+template <int MODE = UR_ON, typename LN, typename Cols, typename UO>
 __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const LN& L, int a, int b, uint32_t usep,
-                                                 Arena& A, Cols& C, int64_t li, UO& o, UriWalk& Wk) {
+                                                 Arena& A, Cols& C, int64_t li, UO& o, UriWalk& Wk,
+                                                 int rfa = -1, bool noamp = false) {
     const UriStage& U = P.uri[u];
     const int qsi = U.want_query ? U.query_stage : -1;
     QueryTable& T = Wk.T;
@@ -3450,7 +3466,8 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
         // dissector reads them back as US-ASCII (U+FFFD each); not on the device
         if (c >= 0x80) { st = ST_FALLBACK; return false; }
         if (c == '%') {
-            if (q + 2 >= b || !is_hex(L[q + 1]) || !is_hex(L[q + 2])) { st = ST_FALLBACK; return false; }  // BAD_EXCAPE_PATTERN
+            if constexpr (MODE != UR_DONE)
+                if (q + 2 >= b || !is_hex(L[q + 1]) || !is_hex(L[q + 2])) { st = ST_REPAIR; return false; }  // BAD_EXCAPE_PATTERN
             if (first_pct < 0) first_pct = q;
             rewr |= h >= 0 ? 1u : 0u;
             if (T.on && h < 0) T.lp = q;
@@ -3461,17 +3478,21 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
                 T.on = false;  // the rawQuery ends at the first '#'
             }
             if (h < 0) h = q;
-            if (q + 1 < b) {
-                const uint32_t d = L[q + 1];
-                if (d == '&' || d == '?' || d == 'x') { st = ST_FALLBACK; return false; }  // HASH_AMP, ALMOST_HTML_ENCODED
+            if constexpr (MODE != UR_DONE) {
+                if (q + 1 < b) {
+                    const uint32_t d = L[q + 1];
+                    if (d == '&' || d == '?' || d == 'x') { st = ST_REPAIR; return false; }  // HASH_AMP, ALMOST_HTML_ENCODED
+                }
+                if (q > a && L[q - 1] == '=') { st = ST_REPAIR; return false; }  // EQUALS_HASH
             }
-            if (q > a && L[q - 1] == '=') { st = ST_FALLBACK; return false; }  // EQUALS_HASH
         } else if (c == ';') {
             // unescapeHtml4 candidate: [&?][a-zA-Z0-9#]*;
-            int r = q - 1;
-            while (r >= a && (is_alnum(L[r]) || L[r] == '#')) --r;
-            if (r >= a && (L[r] == '&' || L[r] == '?')) { st = ST_FALLBACK; return false; }
-        } else if (c == '&' || c == '?') {
+            if constexpr (MODE != UR_DONE) {
+                int r = q - 1;
+                while (r >= a && (is_alnum(L[r]) || L[r] == '#')) --r;
+                if (r >= a && (L[r] == '&' || L[r] == '?')) { st = ST_REPAIR; return false; }
+            }
+        } else if ((c == '&' || c == '?')) {
             rewr |= (c == '?' && fa >= 0 && h < 0) ? 2u : 0u;  // a later '?' becomes '&'
             if (T.on) {
                 T.emit(A.p, q);
@@ -3494,8 +3515,15 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
         return true;
     });
     LP_PROF(52 + 4 * u);
-    if (st != ST_OK) return st;
-    if (T.set) {
+    // UR_OFF keeps the control flow the stage had before the repair existed
+    // (ST_REPAIR leaves like any other status: the kernel queues the line).
+    // UR_ON: a walk that stopped with ST_REPAIR abandons the table it began
+    // (slots beyond A.used, neither used nor counted as slack: the repaired
+    // stage spills a table of its own)
+    bool fix = false;
+    if constexpr (MODE == UR_ON) fix = st == ST_REPAIR;
+    if (st != ST_OK && !fix) return st;
+    if (!fix && T.set) {
         if (T.on) T.emit(A.p, b);
         A.used = T.reg;
         A.slack += 16 * (T.maxp - T.count);  // unused slots
@@ -3505,7 +3533,15 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
         o.qpend.set(qsi, T.count);
     }
     LP_PROF(30 + 8 * u);
-    if (nh > 1) return ST_FALLBACK;                                                       // DOUBLE_HASH
+    if constexpr (MODE == UR_OFF) {
+        if (nh > 1) return ST_REPAIR;                                                     // DOUBLE_HASH
+    } else if constexpr (MODE == UR_ON) {
+        if (!fix && nh > 1) {                                                             // DOUBLE_HASH
+            fix = true;
+            if (T.set) o.qpend.set(qsi, 0);  // (the repaired stage completes its own pieces)
+        }
+        if (fix) return uri_repair(P, u, L, a, b, A, C, li);
+    }
     int pend = b;                              // end of path: first '?'(=fa) or '#'
     if (fa >= 0 && fa < pend) pend = fa;
     if (h >= 0 && h < pend) pend = h;
@@ -3618,14 +3654,14 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
             // the ref is formed before the scan below: with it formed after,
             // the gfx950 build (ROCm 7.2, -O3) delivered a wrong offset on
             // lanes whose scan ran an extra word (parity tests caught it)
-            const uint64_t amp_ref = src_ref(L, qs0, qe - qs0) | REF_AMP;
+            const uint64_t amp_ref = src_ref(L, qs0, qe - qs0) | (MODE == UR_DONE && noamp ? 0ull : REF_AMP);
             if (!(rewr & 2u)) {
                 C.u_query[u][li] = amp_ref;
             } else {
                 Arena X;  // '&' + the query, URIUtil-escaped bytes tripled
                 if (!spill(A, 1u + 3u * (uint32_t)(qe - qs0), X)) return ST_FALLBACK;
                 const uint32_t st = X.used;
-                X.put('&');
+                if (!(MODE == UR_DONE && noamp)) X.put('&');
                 for (int q = fa + 1; q < qe; ++q) {
                     uint32_t c = L[q];
                     if (c == '?') X.put('&');
@@ -3651,7 +3687,7 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
             const uint32_t st = X.used;
             for (int q = h + 1; q < b;) {
                 uint32_t c = L[q];
-                if (q == fa) { X.put('?'); X.put('&'); ++q; }
+                if (q == fa) { X.put('?'); if (!(MODE == UR_DONE && noamp)) X.put('&'); ++q; }
                 else if (c == '?') { X.put('&'); ++q; }
                 else if (c == '%') { X.put(hexv(L[q + 1]) * 16 + hexv(L[q + 2])); q += 3; }
                 else { X.put(c); ++q; }
@@ -3667,12 +3703,30 @@ __host__ __device__ LP_INLINE int uri_stage_rest(const Program& P, int u, const 
 }
 
 // HttpUriDissector fast path on the line bytes [a,b).  Returns status.
-template <typename LN, typename Cols, typename UO>
+template <int MODE = UR_ON, typename LN, typename Cols, typename UO>
 __host__ __device__ LP_INLINE int uri_stage(const Program& P, int u, const LN& L, int a, int b, uint32_t usep, Arena& A,
-                                            Cols& C, int64_t li, UO& o) {
+                                            Cols& C, int64_t li, UO& o, int rfa = -1, bool noamp = false) {
     UriWalk Wk;
-    uri_walk_fast(P, u, L, a, b, usep, A, Wk);
-    return uri_stage_rest(P, u, L, a, b, usep, A, C, li, o, Wk);
+    if constexpr (MODE == UR_DONE) {
+        // a repaired string: its first '?' / '&' is at rfa (-1: none), and a
+        // '&' before it is text that an entity made.  Up to there only '%'
+        // and '#' count; the general walk takes over at rfa
+        const int e = rfa < 0 ? b : rfa;
+        for (int q = a; q < e; ++q) {
+            const uint32_t c = L[q];
+            if (c == '%') {
+                if (Wk.first_pct < 0) Wk.first_pct = q;
+                Wk.rewr |= Wk.h >= 0 ? 1u : 0u;
+            } else if (c == '#') {
+                ++Wk.nh;
+                if (Wk.h < 0) Wk.h = q;
+            }
+        }
+        Wk.resume = rfa;
+    } else {
+        uri_walk_fast(P, u, L, a, b, usep, A, Wk);
+    }
+    return uri_stage_rest<MODE>(P, u, L, a, b, usep, A, C, li, o, Wk, rfa, noamp);
 }
 
 // The pending query pieces of one line, one after the other (the test-only
@@ -3724,9 +3778,9 @@ __host__ __device__ LP_INLINE int derived_source(const Program& P, const UriStag
 // Derived stage u on source [a, b) of L: the URI stage, then its query
 // pieces one after the other.  R: the line's region with the shard's spill
 // allocator (the stage's query table and every rewritten part are spilled).
-template <typename LN, typename Cols>
+template <int MODE = UR_ON, typename LN, typename Cols>
 __host__ __device__ LP_INLINE int derived_stage(const Program& P, int u, const LN& L, int a, int b, Arena& R, Cols& C,
-                                                int64_t li) {
+                                                int64_t li, int rfa = -1, bool noamp = false) {
     uint32_t usep;
     const uint32_t need = uri_need(P, u, L, a, b, usep);
     Arena X = R;
@@ -3735,13 +3789,185 @@ __host__ __device__ LP_INLINE int derived_stage(const Program& P, int u, const L
     o.qlist.fill(0);
     o.qpend.fill(0);
     o.status = ST_OK;
-    int st = uri_stage(P, u, L, a, b, usep, X, C, li, o);
+    int st = uri_stage<MODE>(P, u, L, a, b, usep, X, C, li, o, rfa, noamp);
     const int qs = P.uri[u].query_stage;
     if (st == ST_OK && qs >= 0)
         for (uint32_t k = 0; k < o.qpend.get(qs); ++k)
             query_piece(P, P.query[qs], L, X, (LP_G uint64_t*)(X.p + o.qlist.get(qs) + 16 * k));
     if (X.ovf) R.ovf = true;
     return X.ovf ? ST_FALLBACK : st;
+}
+
+// ---- Malformed URIs (HttpUriDissector.dissect, :160-186): between the
+// '?' / '&' normalisation and URI.create the reference repairs the string:
+// BAD_EXCAPE_PATTERN -> "%25$1" (replaceAll, twice), ALMOST_HTML_ENCODED
+// ("#xHH;" not after '&' gets its '&'), StringEscapeUtils.unescapeHtml4,
+// "=#" -> "=", "#&" -> "&", and every '#' but the last -> '~'.  uri_repair
+// restates that chain, pass by pass in the reference's order, on a copy of
+// the source [a, b) spilled from the region's shard, and then runs the URI
+// stage and its query pieces over the copy (derived_stage, UR_DONE).
+//
+// The copy holds the source's own bytes plus the repairs only: the stage
+// applies URIUtil's escapes and the '?' / '&' normalisation itself, as for
+// any URI.  (URIUtil.encode runs before the chain in the reference; it
+// commutes with it: an escaped byte starts with '%', a non-hex byte, as the
+// raw byte was, and no escaped byte is part of a pattern.)  So a raw '?' is
+// read as the '&' the reference made of it: as an entity start, before
+// "#xHH;" and after '#'.  The first '?' / '&' (fa) is "?&" by then: a '#'
+// before it is not followed by '&', and an entity there keeps the '?'.
+//
+// unescapeHtml4 as the oracle restates it: "&amp;" and the numeric
+// entities that yield A-Z a-z 0-9 - _ . = & are replaced; a candidate the
+// unescaper leaves alone is text; everything else (other named entities,
+// other code points) is FALLBACK.  Two results are more than "the source's
+// bytes plus repairs", and the stage is told of them (UR_DONE: rfa, noamp):
+// an entity at fa is the '&' of "?&" plus its digits, so any value but '&'
+// leaves a rawQuery without the leading '&' (noamp); a '&' that an entity
+// makes before fa is text, so the stage is given fa's place in the copy (rfa)
+// and does not look for it.
+template <typename LN, typename Cols>
+__host__ __device__ LP_INLINE int uri_repair(const Program& P, int u, const LN& L, int a, int b, Arena& R, Cols& C,
+                                             int64_t li) {
+    int n = b - a;
+    // two buffers, the passes copy from one to the other.  Their size: a
+    // '%' starts a match of BAD_EXCAPE_PATTERN at most once in the two
+    // passes ("%25" itself is valid) and then grows by two bytes,
+    // ALMOST_HTML_ENCODED adds one byte per "#x", the later passes shrink
+    uint32_t grow = 0;
+    for (int q = a; q < b; ++q) {
+        const uint32_t c = L[q];
+        grow += c == '%' ? 2u : c == '#' ? 1u : 0u;
+    }
+    const uint32_t cap = ((uint32_t)n + grow + 8u + 3u) & ~3u;
+    Arena B;
+    if (!spill(R, 2u * cap, B)) return ST_FALLBACK;
+    LP_G uint8_t* const p = R.p;
+    uint32_t so = B.used, dn = B.used + cap;  // region offsets of the current string and the next
+    int fa = -1;                              // the first '?' / '&' of the current string
+    for (int q = 0; q < n; ++q) {
+        const uint32_t c = L[a + q];
+        if (c >= 0x80) return ST_FALLBACK;
+        if (fa < 0 && (c == '&' || c == '?')) fa = q;
+        p[so + q] = (uint8_t)c;
+    }
+    auto amp = [](uint32_t c) { return c == '&' || c == '?'; };
+    int m = 0, nfa = -1;                      // the next string's length and fa
+    bool noamp = false;                       // an entity took the '&' of the "?&" at fa: the rawQuery has no leading '&'
+    bool over = false;                        // (never: see cap)
+    auto copy = [&](int i) {
+        if ((uint32_t)m >= cap) { over = true; return; }
+        if (i == fa) nfa = m;
+        p[dn + m++] = p[so + i];
+    };
+    auto flip = [&]() {
+        const uint32_t t = so;
+        so = dn;
+        dn = t;
+        n = m;
+        fa = nfa;
+        m = 0;
+        nfa = -1;
+    };
+    // BAD_EXCAPE_PATTERN %([^0-9a-fA-F]|[0-9a-fA-F][^0-9a-fA-F]|.$|$) -> %25$1, twice
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int i = 0; i < n;) {
+            int g = -1;  // length of $1 (-1: no match here)
+            if (p[so + i] == '%') {
+                if (i + 1 >= n) g = 0;
+                else if (!is_hex(p[so + i + 1])) g = 1;
+                else if (i + 2 >= n) g = 1;
+                else if (!is_hex(p[so + i + 2])) g = 2;
+            }
+            if (g < 0) { copy(i++); continue; }
+            if ((uint32_t)m + 8u > cap) return ST_FALLBACK;  // (never: see cap)
+            p[dn + m++] = '%';
+            p[dn + m++] = '2';
+            p[dn + m++] = '5';
+            ++i;
+            for (int k = 0; k < g; ++k) copy(i++);
+        }
+        flip();
+    }
+    for (int i = 0; i < n; ++i)  // (two passes leave no bad escape; were one left, URI.create would decide)
+        if (p[so + i] == '%' && (i + 2 >= n || !is_hex(p[so + i + 1]) || !is_hex(p[so + i + 2]))) return ST_FALLBACK;
+    // ALMOST_HTML_ENCODED ([^&])(#x[0-9a-fA-F][0-9a-fA-F];) -> $1&$2
+    for (int i = 0; i < n;) {
+        const bool hit = !amp(p[so + i]) && i + 5 < n && p[so + i + 1] == '#' && p[so + i + 2] == 'x' &&
+                         is_hex(p[so + i + 3]) && is_hex(p[so + i + 4]) && p[so + i + 5] == ';';
+        if ((uint32_t)m + 8u > cap) return ST_FALLBACK;  // (never: see cap)
+        copy(i++);
+        if (!hit) continue;
+        p[dn + m++] = '&';
+        for (int k = 0; k < 5; ++k) copy(i++);
+    }
+    flip();
+    // unescapeHtml4
+    for (int i = 0; i < n;) {
+        const uint32_t c = p[so + i];
+        if (amp(c)) {
+            int j = i + 1;
+            while (j < n && is_alnum(p[so + j]) && j - i <= 10) ++j;
+            if (j < n && p[so + j] == ';' && j > i + 1) {
+                if (!(j - i == 4 && p[so + i + 1] == 'a' && p[so + i + 2] == 'm' && p[so + i + 3] == 'p')) return ST_FALLBACK;
+                copy(i);  // "&amp;" -> '&' (the source's own '&' / '?')
+                i = j + 1;
+                continue;
+            }
+            if (i < n - 2 && p[so + i + 1] == '#') {
+                int start = i + 2;
+                bool hex = false;
+                if (p[so + start] == 'x' || p[so + start] == 'X') { ++start; hex = true; }
+                int end = start;
+                while (end < n && is_hex(p[so + end])) ++end;
+                bool ent = end < n && p[so + end] == ';' && end > start;
+                uint64_t v = 0;
+                for (int q = start; q < end && ent; ++q) {
+                    const uint32_t dv = hexv(p[so + q]);
+                    if (!hex && dv > 9) ent = false;
+                    v = v * (hex ? 16u : 10u) + dv;
+                    if (v > 0x7FFFFFFFull) ent = false;
+                }
+                if (ent) {
+                    if (!(is_alnum((uint32_t)v) || v == '-' || v == '_' || v == '.' || v == '=' || v == '&')) return ST_FALLBACK;
+                    // at fa the entity is the '&' of "?&": "?&#38;" stays "?&",
+                    // any other value leaves the '?' alone (noamp).  Elsewhere
+                    // the value is text, a '&' made before fa included (rfa)
+                    if (i == fa) {
+                        copy(i);
+                        noamp = v != '&';
+                    }
+                    if (i != fa || noamp) p[dn + m++] = (uint8_t)v;
+                    i = end + 1;
+                    continue;
+                }
+            }
+        }
+        copy(i++);
+    }
+    flip();
+    // EQUALS_HASH_PATTERN
+    for (int i = 0; i < n;) {
+        const bool hit = p[so + i] == '=' && i + 1 < n && p[so + i + 1] == '#';
+        copy(i);
+        i += hit ? 2 : 1;
+    }
+    flip();
+    // HASH_AMP_PATTERN (at fa the '#' is followed by the '?' of "?&")
+    for (int i = 0; i < n; ++i) {
+        if (p[so + i] == '#' && i + 1 < n && amp(p[so + i + 1]) && i + 1 != fa) continue;
+        copy(i);
+    }
+    flip();
+    // DOUBLE_HASH_PATTERN loop: every '#' but the last becomes '~'
+    int last = -1;
+    for (int i = 0; i < n; ++i) {
+        if (p[so + i] != '#') continue;
+        if (last >= 0) p[so + last] = '~';
+        last = i;
+    }
+    if (over || n > 0xFFFF) return ST_FALLBACK;  // (positions are 16-bit)
+    const ArenaLineT<const LP_G uint8_t*> V{{p + so, 0u, n}, so};
+    return derived_stage<UR_DONE>(P, u, V, 0, n, R, C, li, fa, noamp);
 }
 
 // The derived stages of one OK line of LogFormat fmt.  line: the line's
@@ -3779,7 +4005,7 @@ __host__ __device__ LP_INLINE int derived_line(const Program& P, int fmt, const 
 // Phase 2 of one line (the URI kernel): the URI stages of its LogFormat.
 // lu(u): the line view of stage u's source (holding at least [a, b)), with
 // sp[u] = a | b << 16 (0: no source), usep[u] its event count.
-template <typename LU, typename Cols, typename SP, typename UO>
+template <int MODE = UR_ON, typename LU, typename Cols, typename SP, typename UO>
 __host__ __device__ LP_INLINE void phase2(const Program& P, int fmt, LU&& lu, const SP& sp, const SP& usep, UO& o,
                                           Arena& A, Cols& C, int64_t li) {
     const int nu = P.n_uri < SP::size ? P.n_uri : SP::size;  // the caller picked SP::size >= P.n_uri
@@ -3793,7 +4019,7 @@ __host__ __device__ LP_INLINE void phase2(const Program& P, int fmt, LU&& lu, co
             continue;
         }
         LP_PROF(10 + 2 * u);
-        const int st = uri_stage(P, u, lu(u), a, b, usep.get(u), A, C, li, o);
+        const int st = uri_stage<MODE>(P, u, lu(u), a, b, usep.get(u), A, C, li, o);
         LP_PROF(11 + 2 * u);
         if (st != ST_OK) o.status = st;
     }

@@ -1,6 +1,7 @@
 // gfx950 URI kernels of the logparser_amd engine (HttpUriDissector,
 // QueryStringFieldDissector): k_uri_lines, its direct path k_uri_overflow,
-// and the derived (type-remapped) stages k_derived_lines.  They run after
+// which also redoes the lines whose URI the reference repairs, and the
+// derived (type-remapped) stages k_derived_lines.  They run after
 // the parse kernels, one wave per 64 lines of the batch's line index.
 #include "kernels_common.h"
 
@@ -229,9 +230,12 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
 // SLOT (several LogFormats): pass k runs, on every lane, the k-th URI stage of
 // the lane's own LogFormat (URI stages by slot: the lanes of all formats
 // walk together instead of each format's stages under a partial mask).
-template <int NU, int NQ, bool COOP, bool SLOT, typename LU, typename LL>
+// A line whose URI the reference repairs (ST_REPAIR) is stored as FALLBACK;
+// QUEUE: it is appended to uri_fix_list (k_uri_lines), else `redo` tells the
+// caller to redo it (k_uri_overflow, which also works the list off).
+template <int NU, int NQ, bool COOP, bool SLOT, bool QUEUE, typename LU, typename LL>
 __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, UriLane<NU>& U, LU&& lu, LL&& ll,
-                                         bool active, int64_t li, int64_t wave, WaveCounts& WC) {
+                                         bool active, int64_t li, int64_t wave, WaveCounts& WC, bool& redo) {
     const int lane = lane_id();
     const int nq = P.n_query < NQ ? P.n_query : NQ;
     uint32_t need = 0;
@@ -327,8 +331,8 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
             uri_walk_fast(P, u, lu(u), a, b, U.usep.get(u), A, Wk);
         }
         if (part) {
-            const int st = uri_stage_rest(P, u, lu(u), a, b, U.usep.get(u), A, C, li, o, Wk);
-            if (st != ST_OK) o.status = st;
+            const int st = uri_stage_rest<UR_OFF>(P, u, lu(u), a, b, U.usep.get(u), A, C, li, o, Wk);
+            if (st != ST_OK) o.status = st;  // (ST_REPAIR too: settled where the status is stored)
         }
         LP_PROF(11 + 2 * sl);
     }
@@ -466,6 +470,17 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
         if (((piece_ovf >> lane) & 1) && o.status == ST_OK) o.status = ST_FALLBACK;
     }
     LP_PROF(22);
+    redo = false;
+    if (U.ok && o.status == ST_REPAIR) {
+        // a malformed URI the reference repairs: FALLBACK until the line is redone
+        o.status = ST_FALLBACK;
+        if constexpr (QUEUE) {
+            const unsigned long long k = atomicAdd(&C.meta->uri_fix_lines, 1ull);
+            if (k < (unsigned long long)C.cap_lines) C.uri_fix_list[k] = (uint32_t)li;
+        } else {
+            redo = true;
+        }
+    }
     if (U.ok && o.status != ST_OK) C.status[li] = (uint8_t)o.status;
     for (int d = 32; d > 0; d >>= 1) written += __shfl_xor(written, d);
     const int st = !active ? -1 : U.ok ? o.status : (int)C.status[li];
@@ -482,7 +497,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
 template <int NU, int NQ, bool SLOT, uint32_t CAP>
 __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uint64_t nbytes, const Program& P,
                                             const Columns& C, int64_t wave, int64_t n_lines, uint32_t* cbuf,
-                                            uint64_t* plane, WaveCounts& WC) {
+                                            uint64_t* plane, WaveCounts& WC, bool& redo) {
     const int lane = lane_id();
     const int64_t li = wave * PW + lane;
     const bool active = li < n_lines;
@@ -602,7 +617,7 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
         if (lin) f(LineT<lds_bytes>{(lds_bytes)cbuf, lorig, lend});
         else f(LineT<const LP_G uint8_t*>{lsp - lmis, lmis, lend});
     };
-    uri_wave<NU, NQ, true, SLOT>(P, C, U, lu, ll, active, li, wave, WC);
+    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, WC, redo);
     return true;
 }
 
@@ -622,14 +637,92 @@ __global__ __launch_bounds__(PW, SLOT ? LP_URI_SLOT_WPE : 4) void k_uri_lines(co
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP / 4 + 16];
     __shared__ uint64_t plane[URI_CAP / 64 + 1];
     WaveCounts WC;
-    if (uri_compact<NU, NQ, SLOT, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC)) WC.store(C, wave);
+    bool redo;  // (unused: this kernel queues such lines)
+    if (uri_compact<NU, NQ, SLOT, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC, redo)) WC.store(C, wave);
     else if (lane_id() == 0) C.uri_ovf_list[atomicAdd(&C.meta->uri_ovf_waves, 1ull)] = (uint32_t)wave;
+}
+
+// Redoes line li, for which a URI kernel stored FALLBACK because a URI stage
+// met a malformed URI that the reference repairs (lp_device.h uri_repair):
+// the line read from HBM, its whole phase 2 serially (phase2 with the repair
+// on, the query pieces, the list and pair stages) in a fresh region of the
+// line's shard.  Stores the final status and corrects the owning wave's
+// counts, which that wave has stored (atomics: the lanes here hold lines of
+// different waves).  One line per lane, no wave-level operation inside.
+__device__ __forceinline__ void uri_redo_line(const uint8_t* __restrict__ buf, uint64_t nbytes, const Program& P,
+                                              const Columns& C, int64_t n_lines, int64_t li) {
+    if ((uint64_t)li >= (uint64_t)n_lines) return;  // (never: the URI kernels name their own lines)
+    const uint64_t s = C.line_off[li], e = C.line_off[li + 1] - 1;
+    if (e < s || e - s > 0xFFFFull || e > nbytes) return;  // (never: the line passed phase 1)
+    const int n = crlf_len((int)(e - s), e > s ? buf[e - 1] : 0u);
+    const LP_G uint8_t* ls = (const LP_G uint8_t*)(buf) + s;
+    const uint32_t mis = (uint32_t)((uintptr_t)ls & 3);
+    const LineT<const LP_G uint8_t*> L{ls - mis, mis, n};
+    const int fmt = P.n_fmt > 1 ? (int)C.fmt_id[li] : 0;
+    RegArr<MAX_URI> sp, usep;
+    sp.fill(0);
+    usep.fill(0);
+    uint32_t need = 0;
+    for (int u = 0; u < P.n_uri; ++u) {
+        int a, b;
+        if (P.uri[u].fmt != fmt || !uri_source_cols(P, C, li, u, a, b) || b > n) continue;
+        uint32_t ev;
+        need += uri_need(P, u, L, a, b, ev);
+        sp.set(u, mkspan((uint32_t)a, (uint32_t)b));
+        usep.set(u, ev);
+    }
+    need += list_need(P, fmt, L, C, li) + pair_need(P, fmt, L, C, li);
+    need = (need + 15) & ~15u;
+    // the fresh region: from the shard the line's wave allocates in
+    // (regions start 16-byte aligned, the bump pointer is 4-byte aligned)
+    const int shard = (int)((li / PW) % ARENA_SHARDS);
+    LP_G unsigned long long* top = &C.meta->shard_top[16 * shard];
+    const unsigned long long x = (atomicAdd(top, (unsigned long long)need + 12ull) + 15) & ~15ull;
+    int st = ST_FALLBACK;
+    uint32_t written = 0;
+    if (x + need > C.shard_cap) {
+        atomicAdd(&C.meta->arena_ovf, 1ull);  // the batch is re-run with a larger arena
+    } else {
+        const unsigned long long mine = (unsigned long long)shard * C.shard_cap + x;
+        C.arena_base[li] = mine;
+        Arena A{C.arena + mine, 0, need};
+        A.top = top;
+        A.base = x;
+        A.limit = C.shard_cap;
+        UriOut o;
+        o.qlist.fill(0);
+        o.qpend.fill(0);
+        auto lu = [&](int) { return L; };
+        phase2<UR_ON>(P, fmt, lu, sp, usep, o, A, C, li);
+        if (o.status == ST_OK) query_pieces_serial(P, lu, o, A);
+        if (o.status == ST_OK && (!list_fill(P, fmt, L, A, C, li) || !pair_fill(P, fmt, L, A, C, li))) o.status = ST_FALLBACK;
+        if (A.ovf) {
+            o.status = ST_FALLBACK;
+            atomicAdd(&C.meta->arena_ovf, 1ull);
+        }
+        st = o.status;
+        written = A.used - A.slack + A.extra;
+    }
+    // the URI kernel stored FALLBACK and counted the line so
+    LP_G uint32_t* wc = C.wave_counts + WC_WORDS * (size_t)(li / PW);
+    if (st != ST_FALLBACK) {
+        C.status[li] = (uint8_t)st;
+        atomicAdd(&wc[st == ST_OK ? 1 : 2], 1u);
+        atomicSub(&wc[3], 1u);
+    }
+    if (written) atomicAdd(&wc[4], written);
 }
 
 // The waves k_uri_lines queued (their URI bytes exceed its compact buffer),
 // on a persistent grid: the same path with a buffer four times as large (few
 // waves: their occupancy does not matter), and for a wave exceeding even
-// that, the lines' bytes read from HBM directly.
+// that, the lines' bytes read from HBM directly.  Then the lines k_uri_lines
+// queued for uri_redo_line (its list is complete when this kernel starts),
+// one per lane over the same grid: with an empty list, the usual case, that
+// is one load.  A line of this kernel's own waves that needs the redo is
+// redone by its lane at once, and counted in the upper half of
+// Meta::uri_fix_lines (the lower half is the list's length, read by every
+// block here).
 constexpr uint32_t URI_CAP_OVF = 4 * URI_CAP;
 template <int NU, int NQ, bool SLOT>
 __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__ buf, uint64_t nbytes,
@@ -638,12 +731,14 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
     const Columns& C = args->cols;
     const int64_t n_lines = (int64_t)C.meta->n_lines;
     const uint64_t nq = C.meta->uri_ovf_waves;
+    const uint64_t nfix = min((uint64_t)(uint32_t)C.meta->uri_fix_lines, (uint64_t)C.cap_lines);
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP_OVF / 4 + 16];
     __shared__ uint64_t plane[URI_CAP_OVF / 64 + 1];
     for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
         const int64_t wave = C.uri_ovf_list[q];
         WaveCounts WC;
-        if (!uri_compact<NU, NQ, SLOT, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC)) {
+        bool redo = false;
+        if (!uri_compact<NU, NQ, SLOT, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC, redo)) {
             const WaveLines W = wave_lines(C, wave, n_lines, nbytes);
             UriLane<NU> U = uri_lane<NU>(P, C, W.li, W.active);
             const LP_G uint8_t* ls = (const LP_G uint8_t*)(buf) + W.s;
@@ -651,11 +746,20 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
             const LineT<const LP_G uint8_t*> L{ls - mis, mis, crlf_len_hbm(buf, W)};
             auto lu = [&](int) { return L; };
             auto ll = [&](int lend, auto&& f) { f(LineT<const LP_G uint8_t*>{ls - mis, mis, lend}); };
-            uri_wave<NU, NQ, false, SLOT>(P, C, U, lu, ll, W.active, W.li, wave, WC);
+            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, WC, redo);
         }
         __syncthreads();
         WC.store(C, wave);
+        if (__any(redo)) {
+            __threadfence();  // the wave's counts are stored before a lane corrects them
+            if (redo) {
+                atomicAdd(&C.meta->uri_fix_lines, 1ull << 32);
+                uri_redo_line(buf, nbytes, P, C, n_lines, wave * PW + lane_id());
+            }
+        }
     }
+    for (uint64_t q = (uint64_t)blockIdx.x * PW + (uint64_t)lane_id(); q < nfix; q += (uint64_t)gridDim.x * PW)
+        uri_redo_line(buf, nbytes, P, C, n_lines, (int64_t)C.uri_fix_list[q]);
 }
 
 // Derived URI stages (type-remapped query parameters, lp_device.h

@@ -52,7 +52,10 @@ if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else "logparser_amd/_lib/liblogparser_amd.so"
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
     rows = parse(kernels(lib))
-    print("%-70s %5s %5s %6s %6s %7s" % ("kernel", "vgpr", "sgpr", "vspill", "sspill", "scratch"))
+    # lds: the static LDS bytes (a kernel's dynamic LDS is chosen at launch);
+    # waves: per SIMD by registers alone (512 VGPRs per lane, allocated in 8s, at most 8 waves)
+    print("%-86s %5s %5s %6s %6s %7s %6s %5s" % ("kernel", "vgpr", "sgpr", "vspill", "sspill", "scratch", "lds", "waves"))
     for n, v, s, vs, ss, pr, gs in sorted(rows):
         if flt in n:
-            print("%-70s %5s %5s %6s %6s %7s" % (n[:70], v, s, vs, ss, pr))
+            w = min(8, 512 // max(8, (int(v) + 7) // 8 * 8)) if v.isdigit() else "?"
+            print("%-86s %5s %5s %6s %6s %7s %6s %5s" % (n[:86], v, s, vs, ss, pr, gs, w))
