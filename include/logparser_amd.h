@@ -199,8 +199,10 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * k_parse_ovf_lines; several: routing match + k_parse_lines + its direct
  * path), [4] of it the URI kernels (+ the counter reduction); then the last
  * complete lp_result_table on a device view: [5] k_table_values, [6] the
- * STRING columns' offset scans, [7] k_table_chars.  Returns the number of
- * values written. */
+ * STRING columns' offset scans, [7] k_table_chars; then the last complete
+ * lp_result_table_map on a device view, summed over its columns: [8]
+ * k_map_count and the piece-base scan, [9] k_map_entries and its scans, [10]
+ * k_map_fill and k_map_chars.  Returns the number of values written. */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -357,6 +359,62 @@ typedef struct lp_table_col {
 } lp_table_col;
 int lp_result_table(lp_handle *h, const lp_result *r, int64_t first, int64_t count, lp_table_col *cols, int n_cols,
                     int threads);
+
+/* Wildcard targets of a batch as map columns: for a requested "TYPE:prefix.*"
+ * (STRING:request.firstline.uri.query.*, HTTP.COOKIE:request.cookies.*,
+ * STRING:request.querystring.*, HTTP.SETCOOKIE:response.cookies.*, ...) one
+ * map<string,string> per row -- what the Hadoop record reader registers for a
+ * ".*" field (httpdlog-inputformat/.../ApacheHttpdLogfileRecordReader.java:
+ * 206-208: ParsedRecord.setMultiValueString), the record collects per line
+ * (ParsedRecord.java:178-196: the key is the name after the prefix, a null
+ * value is ignored, a later value of a key replaces the earlier; :210-212
+ * getStringSet) and the Pig Loader returns as a DataType.MAP column
+ * (httpdlog-pigloader/.../Loader.java:227-229, 389-390).  Members are the
+ * values Parsable.addDissection delivers to the wildcard (lp_result_emit's
+ * rule: the wildcard of the value's base and type); a member with an empty
+ * name has the key "".  Java's HashMap has no order; here a surviving entry
+ * stands at the position of its key's last non-null delivery, in delivery
+ * order, the same from a host copy and on the device.
+ * Rows [first, first+count), Arrow MapArray layout:
+ *   valid[k] = 1 when line first+k is OK (its record exists; the map may be
+ *        empty, as for every row of a LogFormat that does not deliver the
+ *        path), 0 for a BAD or FALLBACK line (no entries);
+ *   entry_off[count + 1]: row k's entries are [entry_off[k], entry_off[k + 1]);
+ *   key_off / val_off [entries + 1] into key_chars / val_chars: entry e is
+ *        key_chars[key_off[e], key_off[e + 1]) -> val_chars[val_off[e],
+ *        val_off[e + 1]) (UTF-8; no value validity: a null never enters).
+ * Sizes as lp_result_table: entries_cap (key_off and val_off hold
+ * entries_cap + 1 words, never NULL), key_chars_cap, val_chars_cap; every call
+ * sets entries_len / key_chars_len / val_chars_len to what the rows need.
+ * Returns LP_OK; LP_E_NOMEM when a capacity is too small (all three lengths
+ * set, the arrays' contents undefined: call again); LP_E_MISSING for a path
+ * the handle does not deliver; LP_E_INVALID for a path that is not a wildcard.
+ * threads: host threads to replay with.
+ * On a device view (on_host 0) the columns are built on the GPU from the
+ * piece tables the URI kernels wrote, and every array is a device buffer of
+ * the handle's device.  LP_E_UNSUPPORTED there when something other than one
+ * query-string stage or one cookie / raw query string / Set-Cookie stage per
+ * LogFormat delivers under the prefix (a type remapping below it, two stages
+ * under one name, a dissector's named outputs): build those from a host copy.
+ * lp_last_timing [8..10]: the last device call's phases (piece counts; the
+ * surviving pieces and their scans; offsets and bytes), summed over columns. */
+typedef struct lp_table_map_col {
+    const char *path;
+    uint8_t *valid;
+    int64_t *entry_off;
+    int64_t *key_off;
+    int64_t *val_off;
+    char *key_chars;
+    char *val_chars;
+    uint64_t entries_cap;
+    uint64_t key_chars_cap;
+    uint64_t val_chars_cap;
+    uint64_t entries_len;
+    uint64_t key_chars_len;
+    uint64_t val_chars_len;
+} lp_table_map_col;
+int lp_result_table_map(lp_handle *h, const lp_result *r, int64_t first, int64_t count, lp_table_map_col *cols,
+                        int n_cols, int threads);
 
 /* Description of the compiled device program (for logs/tests), NUL-terminated. */
 int64_t lp_describe(lp_handle *h, char *out, size_t cap);

@@ -54,6 +54,36 @@ class LpTableCol(ctypes.Structure):
                 ("chars_cap", ctypes.c_uint64), ("chars_len", ctypes.c_uint64)]
 
 
+class LpTableMapCol(ctypes.Structure):
+    """lp_table_map_col (include/logparser_amd.h): one Arrow map<string,string> column"""
+    _fields_ = [("path", ctypes.c_char_p), ("valid", ctypes.c_void_p), ("entry_off", ctypes.c_void_p),
+                ("key_off", ctypes.c_void_p), ("val_off", ctypes.c_void_p), ("key_chars", ctypes.c_void_p),
+                ("val_chars", ctypes.c_void_p), ("entries_cap", ctypes.c_uint64), ("key_chars_cap", ctypes.c_uint64),
+                ("val_chars_cap", ctypes.c_uint64), ("entries_len", ctypes.c_uint64),
+                ("key_chars_len", ctypes.c_uint64), ("val_chars_len", ctypes.c_uint64)]
+
+
+MAP_ARRAYS = ("valid", "entry_off", "key_off", "key_chars", "val_off", "val_chars")
+
+
+def maps_from_arrow(valid, entry_off, key_off, key_chars, val_off, val_chars):
+    """The rows of an Arrow map<string,string> column (lp_result_table_map) as
+    Python values: a dict per valid row, in the column's entry order, None for
+    a row that is not valid.  Row k's entries are [entry_off[k], entry_off[k +
+    1]); entry e's key is key_chars[key_off[e], key_off[e + 1]), its value
+    val_chars[val_off[e], val_off[e + 1]) (UTF-8)."""
+    kc, vc = bytes(bytearray(key_chars)), bytes(bytearray(val_chars))
+    eo, ko, vo = ([int(x) for x in a] for a in (entry_off, key_off, val_off))
+    out = []
+    for k in range(len(eo) - 1):
+        if not valid[k]:
+            out.append(None)
+            continue
+        out.append({kc[ko[e]:ko[e + 1]].decode("utf-8"): vc[vo[e]:vo[e + 1]].decode("utf-8")
+                    for e in range(eo[k], eo[k + 1])})
+    return out
+
+
 class LpResult(ctypes.Structure):
     """lp_result (include/logparser_amd.h): the SoA results of one batch"""
     _fields_ = [("n_lines", ctypes.c_int64), ("first_line", ctypes.c_int64), ("input_bytes", ctypes.c_uint64),
@@ -145,6 +175,9 @@ def lib():
     L.lp_result_table.restype = ctypes.c_int
     L.lp_result_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
                                   ctypes.POINTER(LpTableCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_table_map.restype = ctypes.c_int
+    L.lp_result_table_map.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
+                                      ctypes.POINTER(LpTableMapCol), ctypes.c_int, ctypes.c_int]
     L.lp_casts.restype = ctypes.c_int
     L.lp_casts.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     L.lp_describe.restype = ctypes.c_int64
@@ -432,6 +465,111 @@ class BatchResult:
         t = (ctypes.c_float * 8)()
         lib().lp_last_timing(self._p._h, t, 8)
         return {"values": t[5], "scans": t[6], "chars": t[7]}
+
+    def _map_call(self, res, paths, first, count, threads, alloc, bufs):
+        """lp_result_table_map with lp_result_table's size protocol: a first
+        call with the buffers at hand, a second after alloc() made the ones
+        that were too small.  bufs: per path {name: array} (MAP_ARRAYS)."""
+        ptr = (lambda a: a.data_ptr()) if hasattr(bufs[0]["valid"], "data_ptr") else (lambda a: a.ctypes.data)
+        size = lambda a: int(a.numel()) if hasattr(a, "numel") else int(a.size)
+        cols = (LpTableMapCol * len(paths))()
+
+        def bind():
+            for k, path in enumerate(paths):
+                c, b = cols[k], bufs[k]
+                c.path = path.encode()
+                c.valid, c.entry_off = ptr(b["valid"]), ptr(b["entry_off"])
+                c.key_off, c.val_off = ptr(b["key_off"]), ptr(b["val_off"])
+                c.key_chars, c.val_chars = ptr(b["key_chars"]), ptr(b["val_chars"])
+                c.entries_cap = min(size(b["key_off"]), size(b["val_off"])) - 1
+                c.key_chars_cap, c.val_chars_cap = size(b["key_chars"]), size(b["val_chars"])
+        bind()
+        L = lib()
+        rc = L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)
+        if rc == LP_E_NOMEM:
+            for k in range(len(paths)):
+                c, b = cols[k], bufs[k]
+                if c.entries_len > c.entries_cap:
+                    b["key_off"], b["val_off"] = alloc(c.entries_len + 1, np.int64), alloc(c.entries_len + 1, np.int64)
+                if c.key_chars_len > c.key_chars_cap:
+                    b["key_chars"] = alloc(c.key_chars_len, np.uint8)
+                if c.val_chars_len > c.val_chars_cap:
+                    b["val_chars"] = alloc(c.val_chars_len, np.uint8)
+            bind()
+            rc = L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)
+        if rc == LP_E_UNSUPPORTED:
+            raise FallbackRequired("a map column's members are derived on the host only: use table_map_from")
+        if rc == LP_E_MISSING:
+            raise MissingDissectorsException("lp_result_table_map: a path the parser does not deliver")
+        if rc != LP_OK:
+            raise ValueError("lp_result_table_map failed: %d" % rc)
+        out = {}
+        for k, path in enumerate(paths):
+            c, b = cols[k], bufs[k]
+            ne = int(c.entries_len)
+            out[path] = {"valid": b["valid"][:count], "entry_off": b["entry_off"][:count + 1],
+                         "key_off": b["key_off"][:ne + 1], "key_chars": b["key_chars"][:int(c.key_chars_len)],
+                         "val_off": b["val_off"][:ne + 1], "val_chars": b["val_chars"][:int(c.val_chars_len)]}
+        return out
+
+    def table_map_from(self, res, paths, first=0, count=None, threads=16, decode=True):
+        """lp_result_table_map from a host copy: for each requested wildcard
+        "TYPE:prefix.*" the Arrow map<string,string> column of rows [first,
+        first+count) -- what ParsedRecord.getStringSet(name) / a Pig MAP
+        column holds per record.  Returns {path: [dict | None per row]}, or
+        with decode=False {path: {name: numpy array}} (MAP_ARRAYS)."""
+        count = self.n_lines - first if count is None else count
+        alloc = lambda n, dt: np.zeros(max(1, n), dtype=dt)
+        bufs = [{"valid": alloc(count, np.uint8), "entry_off": alloc(count + 1, np.int64), "key_off": alloc(1, np.int64),
+                 "val_off": alloc(1, np.int64), "key_chars": np.zeros(0, np.uint8), "val_chars": np.zeros(0, np.uint8)}
+                for _ in paths]
+        out = self._map_call(res, list(paths), first, count, threads, alloc, bufs)
+        if not decode:
+            return out
+        return {p: maps_from_arrow(*(a[n] for n in MAP_ARRAYS)) for p, a in out.items()}
+
+    def table_map_buffers(self, paths, count=None, entries_cap=0, key_chars_cap=0, val_chars_cap=0):
+        """Device buffers for table_map_device(paths, buffers=...): per path
+        {name: torch tensor} (MAP_ARRAYS) with room for count rows, entries_cap
+        entries and that many key / value bytes."""
+        import torch
+        count = self.n_lines if count is None else count
+        dev = torch.device("cuda", self._p.device)
+        mk = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+        return [{"valid": mk(max(1, count), torch.uint8), "entry_off": mk(count + 1, torch.int64),
+                 "key_off": mk(entries_cap + 1, torch.int64), "val_off": mk(entries_cap + 1, torch.int64),
+                 "key_chars": mk(key_chars_cap, torch.uint8), "val_chars": mk(val_chars_cap, torch.uint8)}
+                for _ in paths]
+
+    def table_map_device(self, paths, first=0, count=None, buffers=None, decode=True):
+        """lp_result_table_map on the device view: the map columns built in
+        HBM.  buffers: table_map_buffers(...) to fill (a buffer that is too
+        small is replaced in it) instead of fresh ones.  Returns what
+        table_map_from returns; with decode=False the arrays are torch tensors
+        on the handle's device.  FallbackRequired: the members are derived on
+        the host only (table_map_from answers)."""
+        import torch
+        count = self.n_lines - first if count is None else count
+        res = LpResult()
+        rc = lib().lp_result_view(self._p._h, ctypes.byref(res))
+        if rc != LP_OK:
+            raise EngineUnavailable("lp_result_view failed: %d" % rc)
+        dev = torch.device("cuda", self._p.device)
+        tdt = {np.int64: torch.int64, np.uint8: torch.uint8}
+        alloc = lambda n, dt: torch.empty(max(1, n), dtype=tdt[dt], device=dev)
+        bufs = buffers if buffers is not None else self.table_map_buffers(paths, count)
+        out = self._map_call(res, list(paths), first, count, 0, alloc, bufs)
+        if not decode:
+            return out
+        return {p: maps_from_arrow(*(a[n].cpu().numpy() for n in MAP_ARRAYS)) for p, a in out.items()}
+
+    def table_map_timing(self):
+        """HIP-event ms of the last device lp_result_table_map, summed over
+        its columns: {"count": k_map_count and the piece-base scan, "entries":
+        k_map_entries and its scans, "fill": k_map_fill and k_map_chars}"""
+        t = (ctypes.c_float * 11)()
+        lib().lp_last_timing(self._p._h, t, 11)
+        return {"count": t[8], "entries": t[9], "fill": t[10]}
 
     def record_json_from(self, res, i):
         """lp_result_record_json: the record of line i from a host copy."""

@@ -104,6 +104,8 @@ struct lp_handle {
     hipEvent_t ev[5]{};  // batch start, index done, parse start, batch end, parse kernels done
     hipEvent_t tev[4]{}; // device table: start, values kernel done, scans done, bytes done
     float tms[3] = {0, 0, 0};  // the last device table's values / scans / bytes phases
+    hipEvent_t mev[6]{}; // device map column: start / end of its count, entries and fill phases
+    float mms[3] = {0, 0, 0};  // the last device lp_result_table_map's phases, summed over its columns
     bool have_events = false;
     uint64_t counters[4]{};
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
@@ -648,6 +650,7 @@ lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths,
     if (hipSetDevice(device) != hipSuccess) { if (status) *status = LP_E_DEVICE; return nullptr; }
     for (auto& ev : h->ev) hipEventCreate(&ev);
     for (auto& ev : h->tev) hipEventCreate(&ev);
+    for (auto& ev : h->mev) hipEventCreate(&ev);
     h->have_events = true;
     if (!h->meta.ensure(sizeof(lp::Meta))) { if (status) *status = LP_E_NOMEM; return nullptr; }
     if (status) *status = st;
@@ -664,6 +667,7 @@ void lp_free(lp_handle* h) {
     if (h->have_events) {
         for (auto& ev : h->ev) hipEventDestroy(ev);
         for (auto& ev : h->tev) hipEventDestroy(ev);
+        for (auto& ev : h->mev) hipEventDestroy(ev);
     }
     delete h;
 }
@@ -879,7 +883,8 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     if (st != LP_OK) return st;
     for (int k = 0; k < n && k < 5; ++k) out[k] = h->ms[k];
     for (int k = 5; k < n && k < 8; ++k) out[k] = h->tms[k - 5];
-    return n < 8 ? n : 8;
+    for (int k = 8; k < n && k < 11; ++k) out[k] = h->mms[k - 8];
+    return n < 11 ? n : 11;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1205,6 +1210,233 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
             pos += pr.second;
         }
         C.i64[count] = (int64_t)pos;
+    }
+    return rc;
+}
+
+// ---- wildcard targets as map columns (ParsedRecord.setMultiValueString)
+namespace {
+// one chunk's rows of one map column: per row its entry count, per entry the
+// key / value lengths, and the bytes
+struct MapChunk {
+    std::vector<uint32_t> per_row, klen, vlen;
+    std::string kbytes, vbytes;
+};
+struct MapRowCtx {
+    const std::unordered_map<std::string, std::vector<int>>* by_path;
+    // per column: the row's deliveries in order (key, value, live)
+    struct Item {
+        std::string key, val;
+        bool live;
+    };
+    std::vector<std::vector<Item>>* items;
+    std::vector<std::unordered_map<std::string, size_t>>* last;  // per column: key -> its live item
+};
+void map_member(void* vctx, const std::string& wildcard, const std::string& key, const lp::MVal& v) {
+    MapRowCtx& t = *(MapRowCtx*)vctx;
+    auto it = t.by_path->find(wildcard);
+    if (it == t.by_path->end() || v.null) return;  // ParsedRecord.java:186: a null neither adds nor replaces
+    for (int c : it->second) {
+        auto& items = (*t.items)[c];
+        auto ins = (*t.last)[c].emplace(key, items.size());
+        if (!ins.second) {  // a later value of the key replaces the earlier: the entry moves here
+            items[ins.first->second].live = false;
+            ins.first->second = items.size();
+        }
+        items.push_back({key, v.is_long ? std::to_string(v.l) : std::string((const char*)v.p, v.len), true});
+    }
+}
+}  // namespace
+
+// lp_result_table_map on a device view: the columns built in HBM (table.hip)
+static int table_map_device(lp_handle* h, int64_t first, int64_t count, lp_table_map_col* cols, int n_cols) {
+    if (ensure_synced(h) != LP_OK) return LP_E_STATE;
+    if (first < 0 || count < 0 || first + count > h->n_lines) return LP_E_INVALID;
+    std::vector<lp::MapArgs> args((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) {
+        lp::MapArgs& M = args[(size_t)c];
+        memset(&M, 0, sizeof M);
+        if (!h->plan.table_map_src(cols[c].path, M.src)) return LP_E_UNSUPPORTED;
+        M.first = first;
+        M.count = count;
+        M.valid = cols[c].valid;
+        M.entry_off = cols[c].entry_off;
+        M.key_off = cols[c].key_off;
+        M.val_off = cols[c].val_off;
+        M.key_chars = (uint8_t*)cols[c].key_chars;
+        M.val_chars = (uint8_t*)cols[c].val_chars;
+    }
+    hipSetDevice(h->device);
+    hipStream_t s = h->stream;
+    const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
+    float ms[3] = {0, 0, 0};
+    int rc = LP_OK;
+    for (int c = 0; c < n_cols; ++c) {
+        lp::MapArgs& M = args[(size_t)c];
+        lp_table_map_col& C = cols[c];
+        C.entries_len = C.key_chars_len = C.val_chars_len = 0;
+        // the rows' piece counts and bases
+        if (!h->tscratch.ensure(lp::map_scratch_bytes(count, 0))) return LP_E_NOMEM;
+        const int64_t* d_total = nullptr;
+        int64_t pieces = 0;
+        hipEventRecord(h->mev[0], s);
+        if (lp::launch_map_count(d_args, M, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->mev[1], s);
+        if (hipMemcpyAsync(&pieces, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        float t = 0;
+        hipEventElapsedTime(&t, h->mev[0], h->mev[1]);
+        ms[0] += t;
+        if (pieces >= 0x7FFFFFFF) return LP_E_UNSUPPORTED;  // (the scans count in ints: build it in windows)
+        if (pieces == 0) {  // no entries: every row's map is empty
+            if (hipMemsetAsync(C.entry_off, 0, 8 * ((size_t)count + 1), s) != hipSuccess ||
+                hipMemsetAsync(C.key_off, 0, 8, s) != hipSuccess || hipMemsetAsync(C.val_off, 0, 8, s) != hipSuccess)
+                return LP_E_DEVICE;
+            continue;
+        }
+        // the surviving pieces and their byte totals
+        const size_t need = lp::map_scratch_bytes(count, pieces);
+        if (need > h->tscratch.cap) {  // the scratch moves: the rows' counts and bases again
+            if (!h->tscratch.ensure(need)) return LP_E_NOMEM;
+            if (lp::launch_map_count(d_args, M, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0) return LP_E_DEVICE;
+        }
+        M.n_pieces = pieces;
+        const void* d_tot[3] = {nullptr, nullptr, nullptr};
+        uint32_t entries = 0;
+        int64_t kbytes = 0, vbytes = 0;
+        hipEventRecord(h->mev[2], s);
+        if (lp::launch_map_entries(d_args, M, h->d_buf, h->tscratch.p, h->tscratch.cap, s, d_tot) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->mev[3], s);
+        if (hipMemcpyAsync(&entries, d_tot[0], 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(&kbytes, d_tot[1], 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(&vbytes, d_tot[2], 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return LP_E_DEVICE;
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        hipEventElapsedTime(&t, h->mev[2], h->mev[3]);
+        ms[1] += t;
+        C.entries_len = entries;
+        C.key_chars_len = (uint64_t)kbytes;
+        C.val_chars_len = (uint64_t)vbytes;
+        if (C.entries_len > C.entries_cap || C.key_chars_len > C.key_chars_cap || C.val_chars_len > C.val_chars_cap ||
+            (kbytes && !C.key_chars) || (vbytes && !C.val_chars))
+            rc = LP_E_NOMEM;
+        if (rc != LP_OK) continue;  // (the later columns' lengths still)
+        hipEventRecord(h->mev[4], s);
+        if (lp::launch_map_fill(M, (int64_t)entries, h->tscratch.p, h->tscratch.cap, s) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->mev[5], s);
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        hipEventElapsedTime(&t, h->mev[4], h->mev[5]);
+        ms[2] += t;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+    if (rc == LP_OK)
+        for (int k = 0; k < 3; ++k) h->mms[k] = ms[k];
+    return rc;
+}
+
+int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_map_col* cols, int n_cols,
+                        int threads) {
+    if (!h || !r || !cols || n_cols <= 0) return LP_E_INVALID;
+    std::unordered_map<std::string, std::vector<int>> by_path;
+    for (int c = 0; c < n_cols; ++c) {  // the same validation in both modes
+        const lp_table_map_col& C = cols[c];
+        if (!C.path || !C.valid || !C.entry_off || !C.key_off || !C.val_off) return LP_E_INVALID;
+        const std::string p = C.path;
+        if (p.size() < 2 || p.compare(p.size() - 2, 2, ".*") != 0) return LP_E_INVALID;  // not a wildcard
+        const int casts = h->plan.casts(p);
+        if (casts < 0) return LP_E_MISSING;
+        if (!(casts & LP_CAST_STRING)) return LP_E_INVALID;
+        by_path[p].push_back(c);
+    }
+    if (!r->on_host) {
+        // a device view is only good for the batch the handle holds now
+        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
+            r->line_off != h->line_off.as<uint64_t>())
+            return LP_E_STATE;
+        return table_map_device(h, first, count, cols, n_cols);
+    }
+    if (!r->input) return LP_E_INVALID;
+    if (first < 0 || count < 0 || first + count > r->n_lines) return LP_E_INVALID;
+    lp::ResultView V;
+    make_view(h, *r, V);
+    const int T = std::max(1, std::min(threads > 0 ? threads : 1, 64));
+    const int64_t per = (count + T - 1) / T;
+    std::vector<std::vector<MapChunk>> chunk(T, std::vector<MapChunk>(n_cols));
+    auto work = [&](int t) {
+        const int64_t a = std::min(count, t * per), b = std::min(count, a + per);
+        std::vector<std::vector<MapRowCtx::Item>> items(n_cols);
+        std::vector<std::unordered_map<std::string, size_t>> last(n_cols);
+        MapRowCtx ctx{&by_path, &items, &last};
+        for (int c = 0; c < n_cols; ++c) chunk[t][c].per_row.assign((size_t)(b - a), 0u);
+        for (int64_t k = a; k < b; ++k) {
+            const int64_t i = first + k;
+            const bool ok = V.status && V.status[i] == LP_LINE_OK;
+            for (int c = 0; c < n_cols; ++c) cols[c].valid[k] = ok ? 1 : 0;  // an OK line's record exists: its map may be empty
+            if (!ok) continue;
+            for (int c = 0; c < n_cols; ++c) {
+                items[c].clear();
+                last[c].clear();
+            }
+            h->plan.map_row(V, i, map_member, &ctx);
+            for (int c = 0; c < n_cols; ++c) {
+                MapChunk& M = chunk[t][c];
+                for (const auto& it : items[c]) {
+                    if (!it.live) continue;
+                    ++M.per_row[(size_t)(k - a)];
+                    M.klen.push_back((uint32_t)it.key.size());
+                    M.vlen.push_back((uint32_t)it.val.size());
+                    M.kbytes += it.key;
+                    M.vbytes += it.val;
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
+    work(0);
+    for (auto& th : pool) th.join();
+    // Arrow MapArray: row k = entries [entry_off[k], entry_off[k + 1]); entry e =
+    // key_chars[key_off[e], key_off[e + 1]) -> val_chars[val_off[e], val_off[e + 1])
+    int rc = LP_OK;
+    for (int c = 0; c < n_cols; ++c) {
+        lp_table_map_col& C = cols[c];
+        uint64_t ne = 0, nk = 0, nv = 0;
+        for (int t = 0; t < T; ++t) {
+            ne += chunk[t][c].klen.size();
+            nk += chunk[t][c].kbytes.size();
+            nv += chunk[t][c].vbytes.size();
+        }
+        C.entries_len = ne;
+        C.key_chars_len = nk;
+        C.val_chars_len = nv;
+        if (ne > C.entries_cap || nk > C.key_chars_cap || nv > C.val_chars_cap || (nk && !C.key_chars) ||
+            (nv && !C.val_chars)) {
+            rc = LP_E_NOMEM;
+            continue;
+        }
+        uint64_t e = 0, kpos = 0, vpos = 0;
+        int64_t k = 0;
+        for (int t = 0; t < T; ++t) {
+            const MapChunk& M = chunk[t][c];
+            for (uint32_t n : M.per_row) {
+                C.entry_off[k++] = (int64_t)e;
+                e += n;
+            }
+            uint64_t kp = kpos, vp = vpos, e0 = e - M.klen.size();
+            for (size_t q = 0; q < M.klen.size(); ++q) {
+                C.key_off[e0 + q] = (int64_t)kp;
+                C.val_off[e0 + q] = (int64_t)vp;
+                kp += M.klen[q];
+                vp += M.vlen[q];
+            }
+            if (!M.kbytes.empty()) memcpy(C.key_chars + kpos, M.kbytes.data(), M.kbytes.size());
+            if (!M.vbytes.empty()) memcpy(C.val_chars + vpos, M.vbytes.data(), M.vbytes.size());
+            kpos = kp;
+            vpos = vp;
+        }
+        C.entry_off[count] = (int64_t)e;
+        C.key_off[e] = (int64_t)kpos;
+        C.val_off[e] = (int64_t)vpos;
     }
     return rc;
 }

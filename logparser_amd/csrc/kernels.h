@@ -107,4 +107,22 @@ int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, cons
 int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
                        hipStream_t s);
 
+// a map column of the device table (lp_table.h MapArgs), three launches with a
+// read of totals between them: scratch bytes for count rows whose column has
+// `pieces` pieces (0: not known yet -- the per-row part, which stays where it
+// is when the scratch grows no further);
+//   launch_map_count   valid, the piece counts and bases; *total: the device
+//                      word that will hold the piece count
+//   launch_map_entries (ma.n_pieces set, > 0) the surviving pieces, their
+//                      lengths and the scans; totals[0..2]: the device words
+//                      of the entry count (u32), key bytes and value bytes
+//   launch_map_fill    (the totals fit the caller's buffers) offsets and bytes
+// Each binds ma's scratch pointers itself.
+size_t map_scratch_bytes(int64_t count, int64_t pieces);
+int launch_map_count(const DeviceArgs* d_args, MapArgs& ma, void* scratch, size_t scratch_bytes, hipStream_t s,
+                     const int64_t** total);
+int launch_map_entries(const DeviceArgs* d_args, MapArgs& ma, const uint8_t* buf, void* scratch, size_t scratch_bytes,
+                       hipStream_t s, const void* totals[3]);
+int launch_map_fill(MapArgs& ma, int64_t n_entries, void* scratch, size_t scratch_bytes, hipStream_t s);
+
 }  // namespace lp

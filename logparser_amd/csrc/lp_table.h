@@ -74,4 +74,31 @@ struct TableArgs {
     uint8_t names[TABLE_NAMES];
 };
 
+// ---- a map column (lp_result_table_map on a device view): the wildcard's
+// members are the pieces of one query stage (q_count / q_params) or one pair
+// stage (p_count / p_tab) per LogFormat
+enum : int32_t { MS_NONE = 0, MS_QUERY, MS_PAIR };  // a = the stage
+struct MapSrc {
+    int32_t kind, a;
+};
+
+// One column's kernel arguments (passed by value).  Scratch arrays: per row
+// [count + 1] cnt / pbase (piece counts, their exclusive scan: pbase[count] =
+// n_pieces); per piece [n_pieces + 1] flag / eidx (survives, its exclusive
+// scan: eidx[n_pieces] = the entries), klen / vlen (key / value bytes of a
+// surviving piece, else 0) and kpos / vpos (their exclusive scans); ksrc /
+// vsrc [n_pieces] where the bytes are (SW_PTR words), ksrc_e / vsrc_e the
+// same per entry (they reuse klen / vlen, dead after the scans).
+struct MapArgs {
+    int64_t first, count, n_pieces;
+    MapSrc src[MAX_FMT];
+    LP_G uint8_t* valid;
+    LP_G int64_t *entry_off, *key_off, *val_off;
+    LP_G uint8_t *key_chars, *val_chars;
+    LP_G int64_t *cnt, *pbase;
+    LP_G uint32_t *flag, *eidx;
+    LP_G int64_t *klen, *vlen, *kpos, *vpos;
+    LP_G uint64_t *ksrc, *vsrc, *ksrc_e, *vsrc_e;
+};
+
 }  // namespace lp

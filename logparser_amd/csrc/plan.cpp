@@ -1216,6 +1216,59 @@ bool Plan::table_src(const std::string& path, TableSrc out[MAX_FMT], std::string
     return true;
 }
 
+bool Plan::table_map_src(const std::string& path, MapSrc out[MAX_FMT]) const {
+    const size_t colon = path.find(':');
+    for (int f = 0; f < MAX_FMT; ++f) out[f] = MapSrc{MS_NONE, 0};
+    if (colon == std::string::npos || path.size() < colon + 3 || path.compare(path.size() - 2, 2, ".*") != 0 || !device_ok_)
+        return false;
+    const std::string type = path.substr(0, colon), prefix = path.substr(colon + 1, path.size() - colon - 3);
+    const std::string exact = type + ":" + prefix, below = exact + ".";
+    // a value remapped below the prefix is delivered again under its new type, and dissected further
+    for (const auto& rm : remaps_)
+        if (rm.first.size() > prefix.size() && rm.first.compare(0, prefix.size(), prefix) == 0 && rm.first[prefix.size()] == '.')
+            return false;
+    auto under = [](const std::string& name, const std::string& stem) {  // name is stem or below it
+        return name.size() >= stem.size() && name.compare(0, stem.size(), stem) == 0 &&
+               (name.size() == stem.size() || name[stem.size()] == '.');
+    };
+    for (int f = 0; f < prog_.n_fmt; ++f) {
+        int found = 0;
+        if (type == "STRING") {
+            auto q = tqp_[f].find(prefix);
+            if (q != tqp_[f].end()) {
+                if (q->second < 0) return false;
+                out[f] = MapSrc{MS_QUERY, q->second};
+                ++found;
+            }
+        }
+        auto ps = tpair_[f].find(exact);
+        if (ps != tpair_[f].end()) {
+            if (ps->second < 0) return false;
+            out[f] = MapSrc{MS_PAIR, ps->second};
+            ++found;
+        }
+        if (found > 1) return false;
+        // anything else delivering under the prefix: a dissector's named outputs, values only the
+        // replay derives, the pieces of a stage whose name is a stem of the prefix (a cookie's
+        // attributes, a parameter whose name holds a '.')
+        for (const auto* m : {&tsrc_[f], &talt_[f]})
+            for (const auto& kv : *m)
+                if (kv.first.compare(0, below.size(), below) == 0) return false;
+        for (const auto& x : thost_exact_[f])
+            if (x.compare(0, below.size(), below) == 0) return false;
+        for (const auto& h : thost_prefix_[f])
+            if (under(prefix, h) || under(h, prefix)) return false;
+        for (const auto& kv : tqp_[f])
+            if (kv.first != prefix && under(prefix, kv.first) && type == "STRING") return false;
+        for (const auto& kv : tpair_[f]) {
+            const size_t c2 = kv.first.find(':');
+            const std::string kname = kv.first.substr(c2 + 1);
+            if (kname != prefix && under(prefix, kname)) return false;
+        }
+    }
+    return true;
+}
+
 int Plan::casts(const std::string& target) const {
     auto it = casts_.find(target);
     return it == casts_.end() ? -1 : it->second;
@@ -1915,6 +1968,12 @@ struct Plan::Ctx {
     std::vector<std::pair<std::string, MVal>> rec;  // (TYPE:path, value) per setter call
     std::vector<Emission> em;                        // the delivering addDissection calls
     std::deque<std::string> pool;  // formatted date/time strings
+    // map_row: the wildcard deliveries (the wildcard, the member's name, the value)
+    struct Member {
+        const std::string *wild, *key;
+        MVal v;
+    };
+    std::vector<Member>* members = nullptr;
 };
 
 namespace {
@@ -1945,7 +2004,7 @@ static thread_local int t_origin_kind = 0, t_origin_idx = 0, t_fmt = 0;  // t_fm
 // thread and plan: the set / map lookups on strings dominated the replay
 namespace {
 struct EmitDec {
-    std::string complete, needed;
+    std::string complete, needed, wildcard, member;  // member: the name a wildcard's map keys the value by
     const std::vector<Instance>* ins = nullptr;  // further dissectors (useful intermediate)
     const std::set<std::string>* remap = nullptr;  // the name's type remappings
     bool exact = false, wild = false;
@@ -1989,6 +2048,8 @@ void Plan::emit(Ctx& c, const std::string& base, const std::string& type, const 
         }
         d.exact = needed_.count(d.needed) > 0;
         d.wild = needed_.count(wild) > 0;
+        d.wildcard = wild;
+        d.member = name;
         auto rm = remaps_.find(d.complete);
         if (rm != remaps_.end()) {
             d.remap = &rm->second;
@@ -2023,6 +2084,7 @@ void Plan::emit(Ctx& c, const std::string& base, const std::string& type, const 
     }
     if (d.exact) c.rec.emplace_back(d.needed, v);
     if (d.wild) c.rec.emplace_back(d.needed, v);
+    if (d.wild && c.members) c.members->push_back(Ctx::Member{&d.wildcard, &d.member, v});
     if ((d.exact || d.wild || d.remap_needed) && !recursion) c.em.push_back(Emission{base, type, name, v});
 }
 
@@ -2478,6 +2540,15 @@ int Plan::rec_row(const ResultView& R, int64_t i, RecFn fn, void* ctx) const {
     replay(c);
     for (const auto& e : c.rec) fn(ctx, e.first, e.second);
     return (int)c.rec.size();
+}
+
+int Plan::map_row(const ResultView& R, int64_t i, MapFn fn, void* ctx) const {
+    Ctx c{R, i, R.input + R.line_off[i], R.region(i), {}, {}, {}};
+    std::vector<Ctx::Member> members;
+    c.members = &members;
+    replay(c);  // (the memo the members point into is cleared at a row's start only)
+    for (const auto& m : members) fn(ctx, *m.wild, *m.key, m.v);
+    return (int)members.size();
 }
 
 std::string Plan::record_json(const ResultView& R, int64_t i) const {

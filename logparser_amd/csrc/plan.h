@@ -167,6 +167,20 @@ public:
     // alt (optional): per LogFormat the earlier delivery used when out's
     // delivers no value (TC_NONE: none)
     bool table_src(const std::string& path, TableSrc out[MAX_FMT], std::string& names, TableSrc* alt = nullptr) const;
+    // where the device table finds the members of a requested wildcard
+    // "TYPE:prefix.*" (lp_table.h MapSrc), per LogFormat: the query stage or
+    // the pair stage (PK_COOKIE / PK_QUERY / PK_SETC: the value is the piece's
+    // value ref, a Set-Cookie's cookie string) whose pieces are delivered
+    // under the prefix; MS_NONE for a LogFormat that delivers nothing there.
+    // false: something else delivers under it (a type remapping below it, two
+    // stages, a dissector's named outputs): the host replay decides
+    bool table_map_src(const std::string& path, MapSrc out[MAX_FMT]) const;
+    // the members line i delivers to the requested wildcards, in delivery
+    // order: (the wildcard "TYPE:prefix.*", the member's name after the
+    // prefix, its value) -- Parsable.addDissection's wildcard rule
+    // (core/Parsable.java:142-193), as rec_row's
+    using MapFn = void (*)(void* ctx, const std::string& wildcard, const std::string& key, const MVal& v);
+    int map_row(const ResultView& R, int64_t i, MapFn fn, void* ctx) const;
 
 private:
     int build_dissectors(const std::string& logformats, std::string& err);

@@ -587,6 +587,192 @@ __global__ __launch_bounds__(64 * CW) void k_table_chars(const DeviceArgs* __res
     }
 }
 
+// ---- map columns (lp_result_table_map on a device view): a wildcard target
+// "TYPE:prefix.*" as an Arrow map<string,string> per row -- ParsedRecord's
+// setMultiValueString (httpdlog-inputformat/.../ParsedRecord.java:178-196: the
+// key is the name after the prefix, a null is ignored, a later value of a key
+// replaces the earlier) over the piece table of the query / pair stage that
+// delivers the wildcard's members (lp_table.h MapArgs):
+//
+//   k_map_count    one lane per row: the validity byte, the row's piece count
+//   (scan)         the counts -> piece bases
+//   k_map_entries  one lane per PIECE (a 300-piece line is 300 lanes, not one):
+//                  its row by a binary search over the piece bases; it
+//                  survives when its name was requested and no later piece of
+//                  the row has the same name; key / value lengths and where
+//                  their bytes are (SW_PTR words: names and values are refs)
+//   (scans)        the survive flags -> entry indices; the lengths -> offsets
+//   k_map_fill     entry_off per row, key_off / val_off and the source words
+//                  per surviving piece, compacted to its entry
+//   k_map_chars    one wave per 64 entries of the keys (grid y 0) or values
+//                  (1): k_table_chars' destination-major walk
+//
+// An entry stands at the position of its key's last piece: the order the host
+// replay (capi.cpp) produces too.
+
+// the row's piece table of the column's source (null: none)
+__device__ __forceinline__ const LP_G uint64_t* map_table(const Program& P, const Columns& C, const MapArgs& M, int64_t i,
+                                                          const LP_G uint8_t* region) {
+    const MapSrc s = M.src[P.n_fmt > 1 ? (int)C.fmt_id[i] : 0];
+    if (s.kind == MS_QUERY) return reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.q_params[s.a][i]));
+    if (s.kind == MS_PAIR) return reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.p_tab[s.a][i]));
+    return nullptr;
+}
+
+__global__ __launch_bounds__(TB) void k_map_count(const DeviceArgs* __restrict__ args, const MapArgs M) {
+    const Program& P = args->prog;
+    const Columns& C = args->cols;
+    const int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (k > M.count) return;
+    if (k == M.count) { M.cnt[k] = 0; return; }  // the scan's last item: the piece total
+    const int64_t i = M.first + k;
+    const bool ok = C.status[i] == ST_OK;
+    int64_t n = 0;
+    if (ok) {
+        const MapSrc s = M.src[P.n_fmt > 1 ? (int)C.fmt_id[i] : 0];
+        if (s.kind == MS_QUERY) n = C.q_count[s.a][i];
+        else if (s.kind == MS_PAIR) n = C.p_count[s.a][i];
+    }
+    M.valid[k] = ok ? 1 : 0;  // an OK line has a record: its map may be empty
+    M.cnt[k] = n;
+}
+
+__global__ __launch_bounds__(TB) void k_map_entries(const DeviceArgs* __restrict__ args, const MapArgs M,
+                                                    const uint8_t* buf) {
+    const Program& P = args->prog;
+    const Columns& C = args->cols;
+    const int64_t p = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (p > M.n_pieces) return;
+    if (p == M.n_pieces) {  // the scans' last item: the totals
+        M.flag[p] = 0;
+        M.klen[p] = 0;
+        M.vlen[p] = 0;
+        return;
+    }
+    // the piece's row: the last one whose base is <= p (pbase[count] = n_pieces > p; a row
+    // without pieces shares its base with the next)
+    int64_t lo = 0, hi = M.count;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (M.pbase[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    const int64_t i = M.first + lo;
+    const uint32_t j = (uint32_t)(p - M.pbase[lo]), cnt = (uint32_t)(M.pbase[lo + 1] - M.pbase[lo]);
+    const LP_G uint8_t *line = nullptr, *region = nullptr;
+    row_view(P, C, buf, i, line, region);  // (a row with pieces is OK)
+    const LP_G uint64_t* t = map_table(P, C, M, i, region);
+    const uint64_t nref = t[2 * j], vref = t[2 * j + 1];
+    const uint32_t nlen = ref_len(nref);
+    const LP_G uint8_t* np = (ref_arena(nref) ? region : line) + ref_off(nref);
+    bool live = nref != REF_SKIP;  // a name that was not requested delivers nothing
+    for (uint32_t q = j + 1; q < cnt && live; ++q) {
+        const uint64_t n2 = t[2 * q];
+        if (n2 == REF_SKIP || ref_len(n2) != nlen) continue;
+        const LP_G uint8_t* p2 = (ref_arena(n2) ? region : line) + ref_off(n2);
+        bool same = true;
+        for (uint32_t b = 0; b < nlen && same; ++b) same = np[b] == p2[b];
+        live = !same;  // a later value of the key replaces this one
+    }
+    const uint64_t vp = (uint64_t)(uintptr_t)((ref_arena(vref) ? region : line) + ref_off(vref));
+    M.flag[p] = live ? 1u : 0u;
+    M.klen[p] = live ? (int64_t)nlen : 0;
+    M.vlen[p] = live ? (int64_t)ref_len(vref) + (ref_amp(vref) ? 1 : 0) : 0;
+    M.ksrc[p] = (uint64_t)(uintptr_t)np;
+    M.vsrc[p] = vp | (ref_amp(vref) ? SW_AMP : 0ull);
+}
+
+__global__ __launch_bounds__(TB) void k_map_fill(const MapArgs M) {
+    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (t <= M.count) M.entry_off[t] = (int64_t)M.eidx[M.pbase[t]];
+    if (t > M.n_pieces) return;
+    const uint32_t e = M.eidx[t];
+    if (t == M.n_pieces || M.flag[t]) {  // an entry's start; the last item: the ends of the last entry
+        M.key_off[e] = M.kpos[t];
+        M.val_off[e] = M.vpos[t];
+    }
+    if (t < M.n_pieces && M.flag[t]) {
+        M.ksrc_e[e] = M.ksrc[t];
+        M.vsrc_e[e] = M.vsrc[t];
+    }
+}
+
+// The keys' (blockIdx.y 0) or values' (1) bytes, destination-major: one wave
+// per 64 entries, k_table_chars' walk with every value a SW_PTR word.
+__global__ __launch_bounds__(64 * CW) void k_map_chars(const MapArgs M, int64_t n_entries) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ uint32_t s_off[CW][65];
+    __shared__ uint64_t s_src[CW][64];
+    const bool keys = blockIdx.y == 0;
+    const LP_G int64_t* const eoff = keys ? M.key_off : M.val_off;
+    const LP_G uint64_t* const esrc = keys ? M.ksrc_e : M.vsrc_e;
+    LP_G uint8_t* const out = keys ? M.key_chars : M.val_chars;
+    const int64_t k0 = ((int64_t)blockIdx.x * CW + wv) * 64;
+    if (k0 >= n_entries) return;  // wave-uniform; only wave-level LDS sharing below
+    const int64_t kend = k0 + 64 < n_entries ? k0 + 64 : n_entries;
+    const int nrows = (int)(kend - k0);
+    const int64_t k = k0 + lane;
+    const uint64_t D0 = (uint64_t)eoff[k0], D1 = (uint64_t)eoff[kend];
+    if (lane < nrows) {
+        s_off[wv][lane] = (uint32_t)((uint64_t)eoff[k] - D0);
+        s_src[wv][lane] = esrc[k];
+    }
+    if (lane == 0) s_off[wv][nrows] = (uint32_t)(D1 - D0);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (D1 == D0) return;
+    const uint32_t total = (uint32_t)(D1 - D0);
+    const uint32_t* off = s_off[wv];
+    // 4-byte words of the destination: offsets congruent to -mis mod 4
+    const uint32_t mis = (uint32_t)((uintptr_t)out & 3u);
+    const uint64_t A0 = D0 - ((D0 + mis) & 3u);
+    constexpr int U = 4;  // words per lane per step: the step's loads in flight before its first store
+    for (uint64_t a0 = A0; a0 < D1; a0 += 256 * U) {
+        uint32_t word[U], have[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t d = a0 + 256ull * u + 4ull * (uint64_t)lane;
+            have[u] = 0;
+            word[u] = 0;
+            if (!(d < D1 && d + 4 > D0)) continue;
+            const uint32_t t0 = d < D0 ? (uint32_t)(D0 - d) : 0u;
+            const uint32_t x0 = (uint32_t)(d + t0 - D0);  // the first byte in range, relative
+            int r = 0;
+            for (int st = 32; st; st >>= 1)
+                if (r + st < nrows && off[r + st] <= x0) r += st;
+            uint32_t nxt = off[r + 1], beg = off[r];
+            uint64_t sp = s_src[wv][r];
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t) {
+                const uint32_t x = x0 + t - t0;
+                if (t < t0 || x >= total) continue;
+                while (x >= nxt) {  // the next non-empty entry
+                    ++r;
+                    beg = nxt;
+                    nxt = off[r + 1];
+                    sp = s_src[wv][r];
+                }
+                const uint32_t o = x - beg, amp = (sp & SW_AMP) ? 1u : 0u;
+                const uint8_t b = amp && o == 0
+                                      ? (uint8_t)'&'
+                                      : reinterpret_cast<const LP_G uint8_t*>((uintptr_t)(sp & (SW_AMP - 1)))[o - amp];
+                word[u] |= (uint32_t)b << (8 * t);
+                have[u] |= 1u << t;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t d = a0 + 256ull * u + 4ull * (uint64_t)lane;
+            if (have[u] == 15u) {
+                *reinterpret_cast<LP_G uint32_t*>(out + d) = word[u];
+            } else if (have[u]) {
+                for (uint32_t t = 0; t < 4; ++t)
+                    if ((have[u] >> t) & 1u) out[d + t] = (uint8_t)(word[u] >> (8 * t));
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // scratch: the scan's temporary storage, its sums, the STRING value words
@@ -634,6 +820,112 @@ int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const
     const int64_t waves = (ta.count + 63) / 64;
     hipLaunchKernelGGL(k_table_chars, dim3((unsigned)((waves + CW - 1) / CW), (unsigned)n_str), dim3(64 * CW), 0, s,
                        d_args, d_targs, buf);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- map columns: the scratch of one column (lp_table.h MapArgs).  The per-row
+// arrays come first: their place depends on count alone, so they survive a
+// second layout with the piece count known.
+namespace {
+struct MapLayout {
+    size_t cnt, pbase, tmp, tmp_bytes, flag, eidx, klen, vlen, kpos, vpos, ksrc, vsrc, total;
+};
+MapLayout map_layout(int64_t count, int64_t pieces) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    MapLayout L{};
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += al(bytes); return o; };
+    const size_t rows = (size_t)count + 1, pcs = (size_t)pieces + 1;
+    L.cnt = take(8 * rows);
+    L.pbase = take(8 * rows);
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (const int64_t*)nullptr, (int64_t*)nullptr, (int)rows);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)pcs);
+    hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (const int64_t*)nullptr, (int64_t*)nullptr, (int)pcs);
+    L.tmp_bytes = t1 > t2 ? t1 : t2;
+    L.tmp_bytes = L.tmp_bytes > t3 ? L.tmp_bytes : t3;
+    L.tmp = take(L.tmp_bytes);
+    L.flag = take(4 * pcs);
+    L.eidx = take(4 * pcs);
+    L.klen = take(8 * pcs);
+    L.vlen = take(8 * pcs);
+    L.kpos = take(8 * pcs);
+    L.vpos = take(8 * pcs);
+    L.ksrc = take(8 * pcs);
+    L.vsrc = take(8 * pcs);
+    L.total = at;
+    return L;
+}
+MapLayout map_bind(MapArgs& ma, void* scratch) {
+    const MapLayout L = map_layout(ma.count, ma.n_pieces);
+    char* b = (char*)scratch;
+    // (a C-style cast: in the device pass the members are global-memory pointers)
+    auto at = [&](auto& dst, size_t off) { dst = (std::remove_reference_t<decltype(dst)>)(b + off); };
+    at(ma.cnt, L.cnt);
+    at(ma.pbase, L.pbase);
+    at(ma.flag, L.flag);
+    at(ma.eidx, L.eidx);
+    at(ma.klen, L.klen);
+    at(ma.vlen, L.vlen);
+    at(ma.kpos, L.kpos);
+    at(ma.vpos, L.vpos);
+    at(ma.ksrc, L.ksrc);
+    at(ma.vsrc, L.vsrc);
+    at(ma.ksrc_e, L.klen);
+    at(ma.vsrc_e, L.vlen);
+    return L;
+}
+unsigned blocks_of(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
+}  // namespace
+
+size_t map_scratch_bytes(int64_t count, int64_t pieces) { return map_layout(count, pieces).total; }
+
+int launch_map_count(const DeviceArgs* d_args, MapArgs& ma, void* scratch, size_t scratch_bytes, hipStream_t s,
+                     const int64_t** total) {
+    if (ma.count < 0 || ma.count >= 0x7FFFFFFF) return -1;  // the scan's item count is an int
+    ma.n_pieces = 0;
+    const MapLayout L = map_bind(ma, scratch);
+    if (L.total > scratch_bytes) return -1;
+    const int rows = (int)ma.count + 1;
+    hipLaunchKernelGGL(k_map_count, dim3(blocks_of(rows)), dim3(TB), 0, s, d_args, ma);
+    size_t t = L.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum((char*)scratch + L.tmp, t, (const int64_t*)ma.cnt, (int64_t*)ma.pbase, rows, s) !=
+        hipSuccess)
+        return -1;
+    *total = (const int64_t*)ma.pbase + ma.count;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_map_entries(const DeviceArgs* d_args, MapArgs& ma, const uint8_t* buf, void* scratch, size_t scratch_bytes,
+                       hipStream_t s, const void* totals[3]) {
+    if (ma.n_pieces <= 0 || ma.n_pieces >= 0x7FFFFFFF) return -1;
+    const MapLayout L = map_bind(ma, scratch);
+    if (L.total > scratch_bytes) return -1;
+    const int pcs = (int)ma.n_pieces + 1;
+    hipLaunchKernelGGL(k_map_entries, dim3(blocks_of(pcs)), dim3(TB), 0, s, d_args, ma, buf);
+    void* tmp = (char*)scratch + L.tmp;
+    size_t t = L.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, t, (const uint32_t*)ma.flag, (uint32_t*)ma.eidx, pcs, s) != hipSuccess) return -1;
+    t = L.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, t, (const int64_t*)ma.klen, (int64_t*)ma.kpos, pcs, s) != hipSuccess) return -1;
+    t = L.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, t, (const int64_t*)ma.vlen, (int64_t*)ma.vpos, pcs, s) != hipSuccess) return -1;
+    totals[0] = (const uint32_t*)ma.eidx + ma.n_pieces;
+    totals[1] = (const int64_t*)ma.kpos + ma.n_pieces;
+    totals[2] = (const int64_t*)ma.vpos + ma.n_pieces;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_map_fill(MapArgs& ma, int64_t n_entries, void* scratch, size_t scratch_bytes, hipStream_t s) {
+    if (ma.n_pieces <= 0 || n_entries < 0 || n_entries > ma.n_pieces) return -1;
+    const MapLayout L = map_bind(ma, scratch);
+    if (L.total > scratch_bytes) return -1;
+    const int64_t n = (ma.n_pieces > ma.count ? ma.n_pieces : ma.count) + 1;
+    hipLaunchKernelGGL(k_map_fill, dim3(blocks_of(n)), dim3(TB), 0, s, ma);
+    if (n_entries > 0) {
+        const int64_t waves = (n_entries + 63) / 64;
+        hipLaunchKernelGGL(k_map_chars, dim3((unsigned)((waves + CW - 1) / CW), 2u), dim3(64 * CW), 0, s, ma, n_entries);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
