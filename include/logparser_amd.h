@@ -126,6 +126,10 @@ int64_t lp_possible_paths_remapped(const char *logformats, int max_depth, const 
 #define LP_OPT_ONE_PASS 6      /* several LogFormats: 1 (default) one pass over the input (the chunk kernel
                                   routes every line exactly one format matches; the rest after the
                                   routing scan), 0 the line index, routing and parse passes */
+#define LP_OPT_FIXED_SHAPE 7   /* 1 (default): a handle whose compiled program equals one of the fixed
+                                  shapes (common, combined with every path requested) is parsed by
+                                  that shape's instance of the chunk kernel, lp_counters out[11];
+                                  0: by the instances per program class, as every other program */
 int lp_set_option(lp_handle *h, int option, int64_t value);
 
 /* Capacity for the coming batches: columns for max_lines lines and at least
@@ -187,8 +191,9 @@ int64_t lp_line_record_json(lp_handle *h, int64_t i, char *out, size_t cap);
  * onwards, are not counted; out[10] = lines whose URI stages were redone
  * with the repair on (a malformed URI that HttpUriDissector repairs before
  * URI.create: bad '%' escapes, "&amp;" and numeric entities, "=#", "#&",
- * several '#').
- * Returns the words written (at most 11). */
+ * several '#'), out[11] = the fixed shape whose instance of the chunk kernel
+ * parsed the batch (1 combined, 2 common; 0: none, see LP_OPT_FIXED_SHAPE).
+ * Returns the words written (at most 12). */
 int lp_counters(lp_handle *h, uint64_t *out, int n);
 
 /* Device-side timing of the last batch, in milliseconds, measured with HIP

@@ -14,6 +14,7 @@
 
 #include "../../include/logparser_amd.h"
 #include "kernels.h"
+#include "lp_fixed.h"
 #include "plan.h"
 
 #if defined(LP_PROFILE)
@@ -111,6 +112,7 @@ struct lp_handle {
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
     int32_t chunk_wait = 0;        // LP_OPT_CHUNK_WAIT (tests: 0 default, < 0 defer every chunk not yet reached)
     bool one_pass = true;          // LP_OPT_ONE_PASS: several LogFormats on the chunked one-pass path
+    bool fixed_shape = true;       // LP_OPT_FIXED_SHAPE: the chunk kernel's fixed-shape instances (lp_fixed.h)
     bool chunked = false;          // the last batch ran the chunked parse (line index inside the parse kernel)
     uint64_t ovf_waves = 0;        // waves of the last batch parsed by k_parse_overflow (chunked: lines by k_parse_ovf_lines)
     uint64_t uri_ovf_waves = 0;    // ... whose URI stages ran in k_uri_overflow
@@ -294,6 +296,17 @@ bool simple_program(const lp::Program& P) {
     return true;
 }
 
+// The fixed shape (lp_fixed.h) whose chunk kernel instance parses P: only
+// when every field that instance holds as a constant equals P's, field by
+// field (fixed_shape_of), and P is on the chunked one-pass path with its
+// lines in LDS.  Near-miss formats, requested-field subsets that change the
+// capture slots or stage lists, several LogFormats and LP_OPT_FORCE_DIRECT
+// get FS_NONE: today's instances.
+int fixed_shape_program(const lp::Program& P, bool chunked, bool force_direct) {
+    if (!chunked || force_direct || !simple_program(P)) return lp::FS_NONE;
+    return lp::fixed_shape_of(P);
+}
+
 int enqueue(lp_handle* h, bool sync_count) {
     hipStream_t s = h->stream;
     const uint64_t nbytes = h->nbytes;
@@ -406,6 +419,7 @@ int enqueue(lp_handle* h, bool sync_count) {
                 pl.lit_aware = true;
         }
         pl.simple = simple_program(P);
+        pl.shape = h->fixed_shape && !pl.lit_aware ? fixed_shape_program(P, chunked, h->force_direct) : lp::FS_NONE;
         h->last_launch = pl;
         if (chunked) {
             // look-back words (zeroed), per-chunk counts, the queued line list
@@ -705,6 +719,9 @@ int lp_set_option(lp_handle* h, int option, int64_t value) {
     case LP_OPT_ONE_PASS:
         h->one_pass = value != 0;
         return LP_OK;
+    case LP_OPT_FIXED_SHAPE:
+        h->fixed_shape = value != 0;
+        return LP_OK;
     case LP_OPT_CHUNK_WAIT:
         h->chunk_wait = value == -2 ? -2 : value < 0 ? -1 : (int32_t)std::min<int64_t>(value, 1 << 30);
         return LP_OK;
@@ -845,11 +862,11 @@ int lp_counters(lp_handle* h, uint64_t* out, int n) {
     if (!h || !out) return LP_E_INVALID;
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
-    const uint64_t v[11] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
+    const uint64_t v[12] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
                             (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines,
-                            h->uri_fix_lines};
-    for (int k = 0; k < n && k < 11; ++k) out[k] = v[k];
-    return n < 11 ? n : 11;
+                            h->uri_fix_lines, (uint64_t)h->last_launch.shape};
+    for (int k = 0; k < n && k < 12; ++k) out[k] = v[k];
+    return n < 12 ? n : 12;
 }
 
 int lp_histograms(lp_handle* h, uint64_t* out, int out_on_device) {

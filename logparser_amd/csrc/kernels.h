@@ -49,6 +49,8 @@ struct ParseLaunch {
                                 // its literal (the chunked kernel's instance with literal-aware first candidates)
     bool simple = false;        // one format of the Apache common / combined family (capi simple_program)
     bool multi = false;         // several LogFormats on the one-pass path (routing inside the chunk kernel)
+    int shape = 0;              // the fixed shape whose chunk kernel instance parses the program (lp_fixed.h
+                                // fixed_shape_of; FS_NONE: the instances per program class)
 };
 // The chunked parse kernel's geometry: cb input bytes per chunk (one wave
 // each), an LDS window of win_cap bytes (the chunk, 64 bytes before it, the
@@ -70,6 +72,9 @@ ChunkPlan chunk_plan(const ParseLaunch& a);
 // (C.ovf_list and C.uri_ovf_list: parse_waves(cap_lines) + 1 entries each).
 // C: the host copy of the columns the device holds.
 int launch_parse(const ParseLaunch& a, const DeviceArgs* d_args, const Columns& C, hipStream_t s);
+// k_parse_chunks of the fixed shape a.shape on `grid` blocks (parse_fixed.hip); -1: no such instance
+int launch_chunks_fixed(const ParseLaunch& a, const DeviceArgs* d_args, const ChunkPlan& cp, unsigned grid,
+                        hipStream_t s);
 // the URI kernels of a launch (uri.hip)
 int launch_uri(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s);
 // meta->counters[0..5] += the sum of n_entries count records (per_group: of
@@ -78,6 +83,8 @@ int launch_reduce_counts(const uint32_t* d_wave_counts, int64_t n_entries, bool 
 #if defined(LP_PROFILE)
 int prof_read_parse(unsigned long long* out);
 int prof_clear_parse();
+int prof_read_parse_fixed(unsigned long long* out);  // (the fixed-shape instances' own points, parse_fixed.hip)
+int prof_clear_parse_fixed();
 int prof_read_uri(unsigned long long* out);
 int prof_clear_uri();
 #endif

@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "lp_program.h"
+#include "lp_fixed.h"
 
 namespace lp {
 
@@ -133,6 +134,7 @@ typedef const __attribute__((address_space(3))) uint64_t* lds_u64;
 __device__ LP_INLINE uint64_t mask_load(lds_u64 p) { return *p; }
 #endif
 struct NoMasks {};
+static_assert((int)MC_QUOTE == fs::ACLS_QUOTE, "lp_fixed.h names the QUOTE class by its value");
 
 // NPL = 2: the two planes of the parse kernel's window (QUOTE, WS, UEV);
 // NPL = 1: one UEV plane only (the URI kernel's compact buffer: only the URI
@@ -1413,6 +1415,41 @@ __host__ __device__ LP_INLINE bool match_first_leaf(const Program& P, const LN& 
     return ok && pos == L.n;
 }
 
+// match_first_leaf<LA, true> of a fixed shape (lp_fixed.h): the same walk
+// unrolled over the shape's elements, each a compile-time constant, so the
+// same lit_at / cand_first fold to the element's own code (no descriptor
+// load, no branch on its kind, capture slot or literal).
+template <int SHAPE, bool LA, int I, typename LN, typename Caps>
+__host__ __device__ LP_INLINE void fixed_leaf_step(const Program& P, const LN& L, Caps& caps, int& pos, bool& ok) {
+    constexpr ElemV e = fixed_shape(SHAPE).elems[I];
+    static_assert(e.lit_len <= 4, "lit_at reads the Program's literal pool for longer literals");
+    LP_PROF_EL_BEGIN();
+    if constexpr (e.kind == EK_LIT) {
+        ok = ok && lit_at(P, L, pos, e);
+        pos += e.lit_len;
+    } else {
+        if (ok) {
+            const int c = cand_first<LA, true>(P, e, L, pos);
+            ok = c >= 0;
+            if constexpr (e.cap >= 0) caps.set_u(e.cap, mkspan(pos, c));
+            pos = ok ? c : pos;
+        }
+    }
+    LP_PROF_EL_END(I);
+}
+template <int SHAPE, bool LA, typename LN, typename Caps, size_t... I>
+__host__ __device__ LP_INLINE bool match_fixed_leaf_(const Program& P, const LN& L, Caps& caps,
+                                                     std::index_sequence<I...>) {
+    int pos = 0;
+    bool ok = true;
+    (fixed_leaf_step<SHAPE, LA, (int)I>(P, L, caps, pos, ok), ...);
+    return ok && pos == L.n;
+}
+template <int SHAPE, bool LA = true, typename LN, typename Caps>
+__host__ __device__ LP_INLINE bool match_fixed_leaf(const Program& P, const LN& L, Caps& caps) {
+    return match_fixed_leaf_<SHAPE, LA>(P, L, caps, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_elems>{});
+}
+
 // The same first leaf for a lane of a several-format program: the lane's
 // own format's elements (LDS in the kernel, a lane-dependent index), caps
 // set by a select chain.  false also when an element needs the DFS's
@@ -2680,6 +2717,96 @@ __host__ __device__ LP_INLINE uint32_t hist_word(const Program& P, const LN& L, 
     return present | (code << 16) | (m << 26);
 }
 
+// The results of time stage t of a line (MULTI: t differs between the lanes).
+template <bool MULTI>
+__host__ __device__ LP_INLINE void time_store(LineOut& o, int t, int64_t ep, uint64_t lo, uint64_t ut, uint32_t ns) {
+    o.tdone |= 1u << t;
+    if constexpr (MULTI) {  // t differs between lanes: select chains
+        o.ep_lo.set(t, (uint32_t)(uint64_t)ep);
+        o.ep_hi.set(t, (uint32_t)((uint64_t)ep >> 32));
+        o.lo_lo.set(t, (uint32_t)lo);
+        o.lo_hi.set(t, (uint32_t)(lo >> 32));
+        o.ut_lo.set(t, (uint32_t)ut);
+        o.ut_hi.set(t, (uint32_t)(ut >> 32));
+        o.nano.set(t, ns);
+    } else {  // t is wave-uniform: indexed register writes
+        o.ep_lo.set_u(t, (uint32_t)(uint64_t)ep);
+        o.ep_hi.set_u(t, (uint32_t)((uint64_t)ep >> 32));
+        o.lo_lo.set_u(t, (uint32_t)lo);
+        o.lo_hi.set_u(t, (uint32_t)(lo >> 32));
+        o.ut_lo.set_u(t, (uint32_t)ut);
+        o.ut_hi.set_u(t, (uint32_t)(ut >> 32));
+        o.nano.set_u(t, ns);
+    }
+}
+
+// First-line stage f on the captured token k of a line that matched.
+// HttpFirstLineDissector: ^([a-zA-Z-_]+) (.*) (HTTP/[0-9]+\.[0-9]+)$ else ^([a-zA-Z-_]+) (.*)$
+template <typename LN>
+__host__ __device__ LP_INLINE void first_line_stage(const LN& L, LineOut& o, int f, int k) {
+    if (o.tok_flags & (1u << k)) return;                  // null
+    const uint32_t sp0 = o.caps.get(k);
+    int a = sp0 & 0xFFFF, b = sp0 >> 16;
+    if (b <= a) return;                                   // empty
+    // method [a-zA-Z-_]+ (SWAR scan for the first other byte)
+    const int q = find_fwd(L, a, b, [](uint32_t w) {
+        const uint32_t l = w | 0x20202020u;
+        const uint32_t alpha = swar::ge(l, 'a') & swar::lt(l, 'z' + 1) & ~(w & swar::HI);
+        return ~(alpha | swar::eq(w, '-') | swar::eq(w, '_')) & swar::HI;
+    });
+    if (q == a || q >= b || L[q] != ' ') return;          // neither regex matches
+    o.fl_method.set(f, mkspan(a, q));
+    int us = q + 1;
+    // protocol: the last ' ' must be followed by HTTP/d+.d+ up to the end
+    int sp = find_space_bwd(L, b - 1, us);
+    if (sp < 0) sp = us - 1;
+    bool full = false;
+    if (sp >= us && b - sp >= 9 && load_u32_at(L, sp + 1) == 0x50545448u /* "HTTP" */ && L[sp + 5] == '/') {
+        const int d1 = sp + 6, r = digits_end(L, d1);
+        if (r > d1 && r < b && L[r] == '.') {
+            const int d2 = r + 1, r2 = digits_end(L, d2);
+            full = r2 >= b && b > d2;  // digits up to the end of the value
+        }
+    }
+    if (full) {
+        o.fl_kind.set(f, FL_FULL);
+        o.fl_uri.set(f, mkspan(us, sp));
+        o.fl_proto.set(f, mkspan(sp + 1, b));
+    } else {
+        o.fl_kind.set(f, FL_CHOPPED);
+        o.fl_uri.set(f, mkspan(us, b));
+        o.fl_proto.set(f, 0);
+    }
+}
+
+// The time and first-line stages of a fixed shape (lp_fixed.h): its stage
+// lists are constants (every time stage TK_APACHE).  false: a time stamp
+// TimeStampDissector rejects (the line is BAD).
+template <int SHAPE, int T, typename LN>
+__host__ __device__ LP_INLINE void fixed_time_step(const LN& L, LineOut& o, bool& ok) {
+    constexpr int k = fixed_shape(SHAPE).time_tok[T];
+    if (!ok) return;
+    int64_t ep;
+    uint64_t lo, ut;
+    if (!parse_apache_time(L, (int)(o.caps.get_u(k) & 0xFFFF), ep, lo, ut)) { ok = false; return; }
+    time_store<false>(o, T, ep * 1000, lo, ut, 0);
+}
+template <int SHAPE, typename LN, size_t... J>
+__host__ __device__ LP_INLINE bool fixed_time_stages(const LN& L, LineOut& o, std::index_sequence<J...>) {
+    bool ok = true;
+    (fixed_time_step<SHAPE, (int)J>(L, o, ok), ...);
+    return ok;
+}
+template <int SHAPE, int F, typename LN>
+__host__ __device__ LP_INLINE void fixed_fl_step(const LN& L, LineOut& o) {
+    constexpr int k = fixed_shape(SHAPE).fl_tok[F];
+    first_line_stage(L, o, F, k);
+}
+template <int SHAPE, typename LN, size_t... J>
+__host__ __device__ LP_INLINE void fixed_fl_stages(const LN& L, LineOut& o, std::index_sequence<J...>) {
+    (fixed_fl_step<SHAPE, (int)J>(L, o), ...);
+}
+
 // Phase 1: guard, match, tokens, time, first line (the parse kernel).
 // clean: the caller already proved every byte of the line passes the
 // fast-path guard (the kernel checks the whole staged window at once).
@@ -2702,8 +2829,12 @@ __host__ __device__ LP_INLINE uint32_t hist_word(const Program& P, const LN& L, 
 // PRE (several LogFormats, one pass): the line's format and its first-leaf
 // spans are already known (fmt_match_word captured them into o.caps, the
 // guard included): phase 1 starts after the match.
-template <bool MULTI = false, bool LA = true, bool SIMPLE = false, bool DFS = true, bool PRE = false, typename LN,
-          typename EL, typename Stk, typename Cols>
+// SHAPE (with SIMPLE, one LogFormat): the program equals the fixed shape
+// (lp_fixed.h fixed_shape_of): the first leaf, the token flags and the time
+// and first-line stages take the elements and stage lists from the shape's
+// constants, unrolled; the rules are the same functions.
+template <bool MULTI = false, bool LA = true, bool SIMPLE = false, bool DFS = true, bool PRE = false, int SHAPE = FS_NONE,
+          typename LN, typename EL, typename Stk, typename Cols>
 __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, const LN& L, LineOut& o, Stk stk, Cols& C,
                                           int64_t li, bool clean = false, int fmt = 0) {
     o.status = ST_OK;
@@ -2741,7 +2872,11 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
         if (match_first_leaf_lane(P, elems + e0, ne, L, o.caps)) st = ST_OK;
         else o.caps.fill(0);  // the DFS sets its own
     } else {
-        if (P.n_fmt == 1 && match_first_leaf<LA, SIMPLE>(P, L, o.caps)) st = ST_OK;
+        if constexpr (SHAPE != FS_NONE) {
+            if (match_fixed_leaf<SHAPE, LA>(P, L, o.caps)) st = ST_OK;
+        } else {
+            if (P.n_fmt == 1 && match_first_leaf<LA, SIMPLE>(P, L, o.caps)) st = ST_OK;
+        }
     }
     if (st != ST_OK) {
         const int e0 = P.fmt_elem0[fmt], ne = P.fmt_elem0[fmt + 1] - e0;
@@ -2755,11 +2890,21 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
     // NGINX: NginxHttpdLogFormatDissector.java:107-119).  Slots unrolled (the
     // spans stay in registers); only one-byte values are read.
     {
-        const bool apache = P.fmt_apache[fmt] != 0;
+        bool apache;
+        int n_tok;
+        if constexpr (SHAPE != FS_NONE) {
+            constexpr bool s_apache = fixed_shape(SHAPE).apache != 0;
+            constexpr int s_n_tok = fixed_shape(SHAPE).n_tok;
+            apache = s_apache;
+            n_tok = s_n_tok;
+        } else {
+            apache = P.fmt_apache[fmt] != 0;
+            n_tok = P.n_tok;
+        }
         bool fb = false;
         uint32_t flags = 0;
         o.caps.each([&](int k, uint32_t sp) {
-            if (k >= P.n_tok) return;
+            if (k >= n_tok) return;
             const int a = sp & 0xFFFF, b = sp >> 16;
             if (b - a == 1) {
                 const uint32_t c = L[a];
@@ -2800,7 +2945,12 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
     }
     LP_PROF(5);
     // TimeStampDissector (MULTI: slot s = the s-th stage of the lane's format)
-    for (int s = 0; s < P.n_time; ++s) {
+    if constexpr (SHAPE != FS_NONE) {
+        if (!fixed_time_stages<SHAPE>(L, o, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_time>{})) {
+            o.status = ST_BAD;
+            return;
+        }
+    } else for (int s = 0; s < P.n_time; ++s) {
         int t = s;
         if constexpr (MULTI) {
             t = -1;
@@ -2830,28 +2980,13 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
             const int st = parse_strf_time(T, L, a, b, ep, lo, ut, ns);
             if (st != ST_OK) { o.status = st; return; }
         }
-        o.tdone |= 1u << t;
-        if constexpr (MULTI) {  // t differs between lanes: select chains
-            o.ep_lo.set(t, (uint32_t)(uint64_t)ep);
-            o.ep_hi.set(t, (uint32_t)((uint64_t)ep >> 32));
-            o.lo_lo.set(t, (uint32_t)lo);
-            o.lo_hi.set(t, (uint32_t)(lo >> 32));
-            o.ut_lo.set(t, (uint32_t)ut);
-            o.ut_hi.set(t, (uint32_t)(ut >> 32));
-            o.nano.set(t, ns);
-        } else {  // t is wave-uniform: indexed register writes
-            o.ep_lo.set_u(t, (uint32_t)(uint64_t)ep);
-            o.ep_hi.set_u(t, (uint32_t)((uint64_t)ep >> 32));
-            o.lo_lo.set_u(t, (uint32_t)lo);
-            o.lo_hi.set_u(t, (uint32_t)(lo >> 32));
-            o.ut_lo.set_u(t, (uint32_t)ut);
-            o.ut_hi.set_u(t, (uint32_t)(ut >> 32));
-            o.nano.set_u(t, ns);
-        }
+        time_store<MULTI>(o, t, ep, lo, ut, ns);
     }
     LP_PROF(6);
     // HttpFirstLineDissector: ^([a-zA-Z-_]+) (.*) (HTTP/[0-9]+\.[0-9]+)$ else ^([a-zA-Z-_]+) (.*)$
-    for (int s = 0; s < P.n_fl; ++s) {
+    if constexpr (SHAPE != FS_NONE) {
+        fixed_fl_stages<SHAPE>(L, o, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_fl>{});
+    } else for (int s = 0; s < P.n_fl; ++s) {
         int f = s;
         if constexpr (MULTI) {
             f = -1;
@@ -2861,40 +2996,7 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
         } else {
             if (P.fl[f].fmt != fmt) continue;
         }
-        int k = P.fl[f].tok;
-        if (o.tok_flags & (1u << k)) continue;                // null
-        const uint32_t sp0 = o.caps.get(k);
-        int a = sp0 & 0xFFFF, b = sp0 >> 16;
-        if (b <= a) continue;                                 // empty
-        // method [a-zA-Z-_]+ (SWAR scan for the first other byte)
-        const int q = find_fwd(L, a, b, [](uint32_t w) {
-            const uint32_t l = w | 0x20202020u;
-            const uint32_t alpha = swar::ge(l, 'a') & swar::lt(l, 'z' + 1) & ~(w & swar::HI);
-            return ~(alpha | swar::eq(w, '-') | swar::eq(w, '_')) & swar::HI;
-        });
-        if (q == a || q >= b || L[q] != ' ') continue;        // neither regex matches
-        o.fl_method.set(f, mkspan(a, q));
-        int us = q + 1;
-        // protocol: the last ' ' must be followed by HTTP/d+.d+ up to the end
-        int sp = find_space_bwd(L, b - 1, us);
-        if (sp < 0) sp = us - 1;
-        bool full = false;
-        if (sp >= us && b - sp >= 9 && load_u32_at(L, sp + 1) == 0x50545448u /* "HTTP" */ && L[sp + 5] == '/') {
-            const int d1 = sp + 6, r = digits_end(L, d1);
-            if (r > d1 && r < b && L[r] == '.') {
-                const int d2 = r + 1, r2 = digits_end(L, d2);
-                full = r2 >= b && b > d2;  // digits up to the end of the value
-            }
-        }
-        if (full) {
-            o.fl_kind.set(f, FL_FULL);
-            o.fl_uri.set(f, mkspan(us, sp));
-            o.fl_proto.set(f, mkspan(sp + 1, b));
-        } else {
-            o.fl_kind.set(f, FL_CHOPPED);
-            o.fl_uri.set(f, mkspan(us, b));
-            o.fl_proto.set(f, 0);
-        }
+        first_line_stage(L, o, f, P.fl[f].tok);
     }
     // ConvertSecondsWithMillisStringDissector on this format's SECOND_MILLIS tokens
     if constexpr (!SIMPLE) for (int sm = 0; sm < P.n_secms; ++sm) {

@@ -17,8 +17,11 @@ import logparser_amd as lpa  # noqa: E402
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4_000_000
 wl = int(os.environ.get("LP_WORKLOAD", "2"))  # BASELINE.json config (lp_synth workload)
 fmt = lpa.SYNTH_FORMATS[wl]
-fields = lpa.get_possible_paths(fmt) if len(sys.argv) < 3 else sys.argv[2].split(",")
 data = lpa.synth(wl, 20261015, 0, n)
+if os.environ.get("LP_PROF_COMMON"):  # the common-format part of the config-2 lines, parsed as "common"
+    fmt = "common"
+    data = b"".join(l.rsplit(b' "', 2)[0] + b"\n" for l in data.split(b"\n")[:-1])
+fields = lpa.get_possible_paths(fmt) if len(sys.argv) < 3 else sys.argv[2].split(",")
 t = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
 p = lpa.HttpdLoglineParser(fmt, fields)
 L = lpa.lib()
@@ -48,7 +51,7 @@ for u in range(2):
 # the parse kernel, then the URI kernel (k_uri_lines): separate orders
 orders = [[0, 60, 1, 2, 3, 4, 5, 14, 15, 16, 6, 7, 9, 61, 62],
           [23, 27, 28, 24, 25, 26, 10, 50, 51, 52, 30, 31, 32, 33, 34, 11, 12, 54, 55, 56, 38, 43, 44, 45, 46, 47, 39, 40, 41, 42, 13, 21, 17, 18, 19, 22]]
-print("parse ms %.3f  waves profiled %d" % (st["ms_parse"], int((T[:, 0] != 0).sum())))
+print("parse ms %.3f  waves profiled %d  fixed shape %s" % (st["ms_parse"], int((T[:, 0] != 0).sum()), st.get("fixed_shape", "-")))
 for order in orders:
     acc = {}
     for w in range(W):
