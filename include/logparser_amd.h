@@ -207,7 +207,9 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * STRING columns' offset scans, [7] k_table_chars; then the last complete
  * lp_result_table_map on a device view, summed over its columns: [8]
  * k_map_count and the piece-base scan, [9] k_map_entries and its scans, [10]
- * k_map_fill and k_map_chars.  Returns the number of values written. */
+ * k_map_fill and k_map_chars; then [11] the last complete lp_result_select on
+ * a device view: k_select_count, the block scan, the host's read of the count
+ * and k_select_write.  Returns the number of values written. */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -420,6 +422,76 @@ typedef struct lp_table_map_col {
 } lp_table_map_col;
 int lp_result_table_map(lp_handle *h, const lp_result *r, int64_t first, int64_t count, lp_table_map_col *cols,
                         int n_cols, int threads);
+
+/* ---- Row selection: dense tables of chosen lines. ----
+ * The reference's consumers never see a row for a line that did not parse:
+ * the Hadoop record reader loops past a line that throws DissectionFailure
+ * ("Ignore bad lines and simply continue") and returns the next good record,
+ * keyed by the line's byte offset (httpdlog-inputformat/.../
+ * ApacheHttpdLogfileRecordReader.java:246-277 nextKeyValue, :283-287
+ * getCurrentKey); the Hive SerDe returns null for it (httpdlog-serde/.../
+ * ApacheHttpdlogDeserializer.java:284-291); the Pig loader reads through the
+ * same record reader.  lp_result_select names the lines of a window whose
+ * status is in a mask; the *_rows calls build the typed table / the map
+ * columns of exactly those lines; the pseudo-columns carry the line's text
+ * and keys.  Together: the dense table of the OK lines (LP_SEL_OK), the few
+ * lines the host parser must redo with their text (LP_SEL_FALLBACK, "@line")
+ * and the key to merge both results ("@lineno" / "@offset").
+ *
+ * lp_result_select: the lines of [first, first+count) whose status is in
+ * status_mask (LP_SEL_* bits), ascending, as batch-relative line indices (NOT
+ * window-relative).  The table's size protocol: *rows_len is always set to the
+ * number of selected lines; LP_E_NOMEM when rows_cap is smaller (nothing is
+ * written then: call again), else LP_OK with rows[0, *rows_len) filled.
+ * Mask 0 selects nothing; a bit other than the three gives LP_E_INVALID.  On
+ * a device view (on_host 0) rows is a device buffer of the handle's device and
+ * the selection is a stream compaction on the GPU (one host read of the count
+ * between its two passes); on a host copy rows is host memory.  State and
+ * window checks as lp_result_table.  lp_counters out[1..3] already are the
+ * exact sizes of a whole-batch select of one status: one call suffices there.
+ * lp_last_timing [11]: the last complete device call (both passes, the scan
+ * and the read of the count between them). */
+#define LP_SEL_OK       (1u << LP_LINE_OK)
+#define LP_SEL_BAD      (1u << LP_LINE_BAD)
+#define LP_SEL_FALLBACK (1u << LP_LINE_FALLBACK)
+int lp_result_select(lp_handle *h, const lp_result *r, int64_t first, int64_t count, uint32_t status_mask,
+                     int64_t *rows, uint64_t rows_cap, uint64_t *rows_len);
+
+/* lp_result_table / lp_result_table_map with row k = line rows[k] (batch-
+ * relative, as lp_result_select writes them): what the record reader and the
+ * SerDe hand on (ApacheHttpdLogfileRecordReader.java:246-287,
+ * ApacheHttpdlogDeserializer.java:284-291) when rows holds the OK lines.  The
+ * indices may come in any order and may repeat (a gather); n_rows may be 0.
+ * Every output array has n_rows (or n_rows + 1) elements, exactly as with
+ * count; return codes and the LP_E_NOMEM / chars_len protocol are those of
+ * the window calls, which are the same implementation with row k = line
+ * first + k.  A row that names a BAD or FALLBACK line is valid 0.  rows is
+ * host memory on a host copy -- an index outside [0, n_lines) returns
+ * LP_E_INVALID before anything is written -- and device memory of the
+ * handle's device on a device view (anything else: LP_E_INVALID), where the
+ * kernels check each index: one outside the batch is never dereferenced, its
+ * row is valid 0 and the call returns LP_E_INVALID.
+ *
+ * Pseudo-columns: lp_table_col.path of lp_result_table and
+ * lp_result_table_rows (both modes) may also be one of four names without a
+ * ':' (so none collides with a "TYPE:path"), valid for EVERY row whatever the
+ * line's status, and needing no lp_casts entry:
+ *   "@line"   STRING only: the line's raw bytes, input[line_off[i],
+ *             line_off[i+1] - 1) less the '\r' of a "\r\n" terminator (the
+ *             parse kernels' line; right for a final line without terminator).
+ *             Not validated: a FALLBACK line may hold invalid UTF-8 or be
+ *             longer than 8191 bytes;
+ *   "@offset" LONG only: line_off[i], the batch-relative LongWritable key
+ *             (ApacheHttpdLogfileRecordReader.java:283-287);
+ *   "@lineno" LONG only: lp_result.first_line + i;
+ *   "@status" LONG only: LP_LINE_*.
+ * Any other kind for them gives LP_E_INVALID.  On a device view of a handle
+ * without a device program (every line FALLBACK) they are LP_E_UNSUPPORTED as
+ * every column is: build them from a host copy. */
+int lp_result_table_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
+                         lp_table_col *cols, int n_cols, int threads);
+int lp_result_table_map_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
+                             lp_table_map_col *cols, int n_cols, int threads);
 
 /* Description of the compiled device program (for logs/tests), NUL-terminated. */
 int64_t lp_describe(lp_handle *h, char *out, size_t cap);

@@ -36,6 +36,12 @@ BUF_HOST, BUF_DEVICE = 0, 1
 OPT_FORCE_DIRECT, OPT_MAX_RETRIES, OPT_ARENA_BYTES, OPT_CHUNK_LINES, OPT_CHUNK_WAIT, OPT_ONE_PASS = 1, 2, 3, 4, 5, 6
 OPT_FIXED_SHAPE = 7  # 0: never the chunk kernel's fixed-shape instances (default 1)
 ARENA_SHARDS = 64
+# lp_result_select's status mask (1 << LINE_*)
+SEL_OK, SEL_BAD, SEL_FALLBACK = 1 << LINE_OK, 1 << LINE_BAD, 1 << LINE_FALLBACK
+# the device select's tiles in lines (csrc/kernels.h SEL_WAVE_LINES / SEL_BLOCK_LINES: one lane takes 16 lines)
+SEL_WAVE_LINES, SEL_BLOCK_LINES = 1024, 4096
+# the pseudo-columns of lp_result_table / lp_result_table_rows: valid for every row whatever its status
+PSEUDO_COLUMNS = {"@line": str, "@offset": int, "@lineno": int, "@status": int}
 
 
 class LpColumn(ctypes.Structure):
@@ -179,6 +185,15 @@ def lib():
     L.lp_result_table_map.restype = ctypes.c_int
     L.lp_result_table_map.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
                                       ctypes.POINTER(LpTableMapCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_select.restype = ctypes.c_int
+    L.lp_result_select.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
+                                   ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.lp_result_table_rows.restype = ctypes.c_int
+    L.lp_result_table_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(LpTableCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_table_map_rows.restype = ctypes.c_int
+    L.lp_result_table_map_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.POINTER(LpTableMapCol), ctypes.c_int, ctypes.c_int]
     L.lp_casts.restype = ctypes.c_int
     L.lp_casts.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     L.lp_describe.restype = ctypes.c_int64
@@ -347,12 +362,76 @@ class BatchResult:
             raise ValueError("lp_result_emit(%d) failed: %d" % (i, rc))
         return out
 
-    def table_from(self, res, columns, first=0, count=None, threads=16, decode=True):
+    def _view(self):
+        res = LpResult()
+        rc = lib().lp_result_view(self._p._h, ctypes.byref(res))
+        if rc != LP_OK:
+            raise EngineUnavailable("lp_result_view failed: %d" % rc)
+        return res
+
+    @staticmethod
+    def _rows_arg(rows, first, count, device):
+        """(pointer, n_rows) of a row list: a contiguous int64 torch tensor on
+        the device (device view) or numpy array (host copy); it excludes a window"""
+        if first != 0 or count is not None:
+            raise ValueError("rows excludes first / count")
+        if device:
+            if not (hasattr(rows, "data_ptr") and rows.is_cuda and str(rows.dtype) == "torch.int64" and rows.is_contiguous()):
+                raise ValueError("rows: a contiguous int64 CUDA tensor expected")
+            return rows.data_ptr(), int(rows.numel())
+        if not (isinstance(rows, np.ndarray) and rows.dtype == np.int64 and rows.flags.c_contiguous and rows.ndim == 1):
+            raise ValueError("rows: a contiguous int64 numpy array expected")
+        return rows.ctypes.data, int(rows.size)
+
+    def _select(self, res, mask, first, count, alloc, ptr):
+        """lp_result_select with the table's size protocol: one call that
+        reports the count, one that fills"""
+        count = self.n_lines - first if count is None else count
+        L = lib()
+        n = ctypes.c_uint64(0)
+        rc = L.lp_result_select(self._p._h, ctypes.byref(res), first, count, mask, None, 0, ctypes.byref(n))
+        if rc not in (LP_OK, LP_E_NOMEM):
+            raise ValueError("lp_result_select failed: %d" % rc)
+        rows = alloc(int(n.value))
+        if n.value:
+            rc = L.lp_result_select(self._p._h, ctypes.byref(res), first, count, mask, ptr(rows), n.value, ctypes.byref(n))
+            if rc != LP_OK:
+                raise ValueError("lp_result_select failed: %d" % rc)
+        return rows
+
+    def select_device(self, mask, first=0, count=None):
+        """lp_result_select on the device view: the lines of [first,
+        first+count) whose status is in mask (SEL_* bits), ascending, as a
+        torch int64 tensor of batch-relative line indices on the handle's
+        device -- the rows= of table_device / table_map_device."""
+        import torch
+        dev = torch.device("cuda", self._p.device)
+        return self._select(self._view(), mask, first, count, lambda n: torch.empty(n, dtype=torch.int64, device=dev),
+                            lambda t: t.data_ptr())
+
+    def select_from(self, res, mask, first=0, count=None):
+        """lp_result_select from a host copy: a numpy int64 array"""
+        return self._select(res, mask, first, count, lambda n: np.empty(n, dtype=np.int64), lambda a: a.ctypes.data)
+
+    def select_timing(self):
+        """HIP-event ms of the last device lp_result_select (both passes, the scan, the host's read of the count)"""
+        t = (ctypes.c_float * 12)()
+        lib().lp_last_timing(self._p._h, t, 12)
+        return t[11]
+
+    def table_from(self, res, columns, first=0, count=None, threads=16, decode=True, rows=None):
         """lp_result_table: typed columns of rows [first, first+count) from a
-        host copy.  columns: [(path, str | int | float)].  Returns {path:
-        (values, valid)}: values a list of str / None for STRING columns
-        (decode=False: the Arrow pair (offsets, chars bytes) as numpy arrays),
-        a numpy int64 / float64 array for BIGINT / DOUBLE ones."""
+        host copy -- or, with rows (a numpy int64 array of line indices, as
+        select_from returns; not together with first / count), of exactly
+        those lines (lp_result_table_rows).  columns: [(path, str | int |
+        float)]; a path may be a pseudo-column (PSEUDO_COLUMNS).  Returns {path:
+        (values, valid)}: values a list of str / None for STRING columns (bytes
+        for "@line", whose text is not validated UTF-8; decode=False: the
+        Arrow pair (offsets, chars bytes) as numpy arrays), a numpy int64 /
+        float64 array for BIGINT / DOUBLE ones."""
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, False)
         count = self.n_lines - first if count is None else count
         kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
         cols = (LpTableCol * len(columns))()
@@ -367,14 +446,17 @@ class BatchResult:
             c.valid, c.i64, c.f64 = valid.ctypes.data, i64.ctypes.data, f64.ctypes.data
             keep.append((valid, i64, f64))
         L = lib()
-        rc = L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), threads)
+        call = (lambda: L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), threads)) \
+            if rows is None else \
+            (lambda: L.lp_result_table_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(columns), threads))
+        rc = call()
         if rc == LP_E_NOMEM:
             for k in range(len(columns)):
                 if cols[k].kind == CAST_STRING:
                     buf = np.zeros(max(1, cols[k].chars_len), dtype=np.uint8)
                     keep[k] = keep[k] + (buf,)
                     cols[k].chars, cols[k].chars_cap = buf.ctypes.data, buf.nbytes
-            rc = L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), threads)
+            rc = call()
         if rc != LP_OK:
             raise ValueError("lp_result_table failed: %d" % rc)
         out = {}
@@ -385,18 +467,23 @@ class BatchResult:
                 out[path] = ((i64, keep[k][3] if len(keep[k]) > 3 else np.zeros(0, np.uint8)), ok)
             elif typ is str:
                 chars = keep[k][3].tobytes() if len(keep[k]) > 3 else b""
-                vals = [chars[i64[j]:i64[j + 1]].decode("utf-8") if ok[j] else None for j in range(count)]
+                text = (lambda b: b) if path == "@line" else (lambda b: b.decode("utf-8"))
+                vals = [text(chars[i64[j]:i64[j + 1]]) if ok[j] else None for j in range(count)]
                 out[path] = (vals, ok)
             else:
                 out[path] = ((i64[:count] if typ is int else f64[:count]).copy(), ok)
         return out
 
-    def table_buffers(self, columns, count=None, chars_cap=None):
+    def table_buffers(self, columns, count=None, chars_cap=None, rows=None):
         """Device buffers for table_device(columns, buffers=...): per column
         [valid, i64 (STRING offsets / BIGINT values), f64 (DOUBLE), chars]
         (None where the kind has none); chars_cap: an int for every STRING
-        column or {path: bytes}."""
+        column or {path: bytes}; rows: a row list (room for that many rows)."""
         import torch
+        if rows is not None:
+            if count is not None:
+                raise ValueError("rows excludes first / count")
+            count = int(rows.numel())
         count = self.n_lines if count is None else count
         dev = torch.device("cuda", self._p.device)
         keep = []
@@ -409,22 +496,28 @@ class BatchResult:
                          torch.empty(max(1, cap), dtype=torch.uint8, device=dev) if typ is str else None])
         return keep
 
-    def table_device(self, columns, first=0, count=None, chars_cap=None, buffers=None):
+    def table_device(self, columns, first=0, count=None, chars_cap=None, buffers=None, rows=None):
         """lp_result_table on the device view: typed columns of rows [first,
-        first+count) built in HBM.  columns: [(path, str | int | float)].
+        first+count) built in HBM -- or, with rows (a torch int64 tensor of
+        line indices on the device, as select_device returns; not together
+        with first / count), of exactly those lines (lp_result_table_rows).
+        columns: [(path, str | int | float)].
         Returns {path: (values, valid)} of torch tensors on the handle's
         device: valid uint8 [count]; STRING columns the Arrow pair (offsets
         int64 [count + 1], chars uint8), BIGINT int64 / DOUBLE float64 [count].
         chars_cap: bytes allotted per STRING column (default: enough after a
         first call that reports the need); buffers: table_buffers(...) to
         fill instead of fresh ones."""
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, True)
         count = self.n_lines - first if count is None else count
         kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
-        res = LpResult()
         L = lib()
-        rc = L.lp_result_view(self._p._h, ctypes.byref(res))
-        if rc != LP_OK:
-            raise EngineUnavailable("lp_result_view failed: %d" % rc)
+        res = self._view()
+        call = (lambda: L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), 0)) \
+            if rows is None else \
+            (lambda: L.lp_result_table_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(columns), 0))
         cols = (LpTableCol * len(columns))()
         keep = buffers if buffers is not None else self.table_buffers(columns, count, chars_cap)
         for k, (path, typ) in enumerate(columns):
@@ -438,7 +531,7 @@ class BatchResult:
             if chars is not None:
                 c.chars = chars.data_ptr()
                 c.chars_cap = chars.numel() if (chars_cap or buffers is not None) else 0
-        rc = L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), 0)
+        rc = call()
         if rc == LP_E_NOMEM:
             import torch
             dev = torch.device("cuda", self._p.device)
@@ -446,7 +539,7 @@ class BatchResult:
                 if typ is str and cols[k].chars_len > cols[k].chars_cap:
                     keep[k][3] = torch.empty(max(1, cols[k].chars_len), dtype=torch.uint8, device=dev)
                     cols[k].chars, cols[k].chars_cap = keep[k][3].data_ptr(), keep[k][3].numel()
-            rc = L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), 0)
+            rc = call()
         if rc == LP_E_UNSUPPORTED:
             raise FallbackRequired("a column's values are derived on the host only: use table_from")
         if rc != LP_OK:
@@ -467,7 +560,7 @@ class BatchResult:
         lib().lp_last_timing(self._p._h, t, 8)
         return {"values": t[5], "scans": t[6], "chars": t[7]}
 
-    def _map_call(self, res, paths, first, count, threads, alloc, bufs):
+    def _map_call(self, res, paths, first, count, threads, alloc, bufs, rows_p=None):
         """lp_result_table_map with lp_result_table's size protocol: a first
         call with the buffers at hand, a second after alloc() made the ones
         that were too small.  bufs: per path {name: array} (MAP_ARRAYS)."""
@@ -486,7 +579,10 @@ class BatchResult:
                 c.key_chars_cap, c.val_chars_cap = size(b["key_chars"]), size(b["val_chars"])
         bind()
         L = lib()
-        rc = L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)
+        call = (lambda: L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)) \
+            if rows_p is None else \
+            (lambda: L.lp_result_table_map_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(paths), threads))
+        rc = call()
         if rc == LP_E_NOMEM:
             for k in range(len(paths)):
                 c, b = cols[k], bufs[k]
@@ -497,7 +593,7 @@ class BatchResult:
                 if c.val_chars_len > c.val_chars_cap:
                     b["val_chars"] = alloc(c.val_chars_len, np.uint8)
             bind()
-            rc = L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)
+            rc = call()
         if rc == LP_E_UNSUPPORTED:
             raise FallbackRequired("a map column's members are derived on the host only: use table_map_from")
         if rc == LP_E_MISSING:
@@ -513,18 +609,23 @@ class BatchResult:
                          "val_off": b["val_off"][:ne + 1], "val_chars": b["val_chars"][:int(c.val_chars_len)]}
         return out
 
-    def table_map_from(self, res, paths, first=0, count=None, threads=16, decode=True):
+    def table_map_from(self, res, paths, first=0, count=None, threads=16, decode=True, rows=None):
         """lp_result_table_map from a host copy: for each requested wildcard
         "TYPE:prefix.*" the Arrow map<string,string> column of rows [first,
         first+count) -- what ParsedRecord.getStringSet(name) / a Pig MAP
         column holds per record.  Returns {path: [dict | None per row]}, or
-        with decode=False {path: {name: numpy array}} (MAP_ARRAYS)."""
+        with decode=False {path: {name: numpy array}} (MAP_ARRAYS).  rows (a
+        numpy int64 array, not together with first / count): row k is line
+        rows[k] (lp_result_table_map_rows)."""
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, False)
         count = self.n_lines - first if count is None else count
         alloc = lambda n, dt: np.zeros(max(1, n), dtype=dt)
         bufs = [{"valid": alloc(count, np.uint8), "entry_off": alloc(count + 1, np.int64), "key_off": alloc(1, np.int64),
                  "val_off": alloc(1, np.int64), "key_chars": np.zeros(0, np.uint8), "val_chars": np.zeros(0, np.uint8)}
                 for _ in paths]
-        out = self._map_call(res, list(paths), first, count, threads, alloc, bufs)
+        out = self._map_call(res, list(paths), first, count, threads, alloc, bufs, rows_p)
         if not decode:
             return out
         return {p: maps_from_arrow(*(a[n] for n in MAP_ARRAYS)) for p, a in out.items()}
@@ -542,24 +643,26 @@ class BatchResult:
                  "key_chars": mk(key_chars_cap, torch.uint8), "val_chars": mk(val_chars_cap, torch.uint8)}
                 for _ in paths]
 
-    def table_map_device(self, paths, first=0, count=None, buffers=None, decode=True):
+    def table_map_device(self, paths, first=0, count=None, buffers=None, decode=True, rows=None):
         """lp_result_table_map on the device view: the map columns built in
         HBM.  buffers: table_map_buffers(...) to fill (a buffer that is too
         small is replaced in it) instead of fresh ones.  Returns what
         table_map_from returns; with decode=False the arrays are torch tensors
         on the handle's device.  FallbackRequired: the members are derived on
-        the host only (table_map_from answers)."""
+        the host only (table_map_from answers).  rows (a torch int64 tensor
+        on the device, not together with first / count): row k is line
+        rows[k] (lp_result_table_map_rows)."""
         import torch
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, True)
         count = self.n_lines - first if count is None else count
-        res = LpResult()
-        rc = lib().lp_result_view(self._p._h, ctypes.byref(res))
-        if rc != LP_OK:
-            raise EngineUnavailable("lp_result_view failed: %d" % rc)
+        res = self._view()
         dev = torch.device("cuda", self._p.device)
         tdt = {np.int64: torch.int64, np.uint8: torch.uint8}
         alloc = lambda n, dt: torch.empty(max(1, n), dtype=tdt[dt], device=dev)
         bufs = buffers if buffers is not None else self.table_map_buffers(paths, count)
-        out = self._map_call(res, list(paths), first, count, 0, alloc, bufs)
+        out = self._map_call(res, list(paths), first, count, 0, alloc, bufs, rows_p)
         if not decode:
             return out
         return {p: maps_from_arrow(*(a[n].cpu().numpy() for n in MAP_ARRAYS)) for p, a in out.items()}

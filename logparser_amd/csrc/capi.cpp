@@ -107,6 +107,8 @@ struct lp_handle {
     float tms[3] = {0, 0, 0};  // the last device table's values / scans / bytes phases
     hipEvent_t mev[6]{}; // device map column: start / end of its count, entries and fill phases
     float mms[3] = {0, 0, 0};  // the last device lp_result_table_map's phases, summed over its columns
+    hipEvent_t sev[2]{}; // device lp_result_select: start, end of its kernels
+    float sel_ms = 0;    // the last device lp_result_select's count pass, scan and write pass
     bool have_events = false;
     uint64_t counters[4]{};
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
@@ -665,6 +667,7 @@ lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths,
     for (auto& ev : h->ev) hipEventCreate(&ev);
     for (auto& ev : h->tev) hipEventCreate(&ev);
     for (auto& ev : h->mev) hipEventCreate(&ev);
+    for (auto& ev : h->sev) hipEventCreate(&ev);
     h->have_events = true;
     if (!h->meta.ensure(sizeof(lp::Meta))) { if (status) *status = LP_E_NOMEM; return nullptr; }
     if (status) *status = st;
@@ -682,6 +685,7 @@ void lp_free(lp_handle* h) {
         for (auto& ev : h->ev) hipEventDestroy(ev);
         for (auto& ev : h->tev) hipEventDestroy(ev);
         for (auto& ev : h->mev) hipEventDestroy(ev);
+        for (auto& ev : h->sev) hipEventDestroy(ev);
     }
     delete h;
 }
@@ -901,7 +905,8 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     for (int k = 0; k < n && k < 5; ++k) out[k] = h->ms[k];
     for (int k = 5; k < n && k < 8; ++k) out[k] = h->tms[k - 5];
     for (int k = 8; k < n && k < 11; ++k) out[k] = h->mms[k - 8];
-    return n < 11 ? n : 11;
+    if (n > 11) out[11] = h->sel_ms;
+    return n < 12 ? n : 12;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1065,15 +1070,33 @@ void table_value(void* vctx, const std::string& target, const lp::MVal& v) {
 }
 }  // namespace
 
-// lp_result_table on a device view: the columns built in HBM (table.hip)
-static int table_device(lp_handle* h, int64_t first, int64_t count, lp_table_col* cols, int n_cols) {
+// Is p memory of the handle's device (what a device view's row list must be:
+// the kernels dereference it)?
+static bool device_memory(lp_handle* h, const void* p) {
+    hipPointerAttribute_t a{};
+    hipSetDevice(h->device);
+    if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer: not a sticky error)
+        return false;
+    }
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == h->device;
+}
+
+// lp_result_table / lp_result_table_rows on a device view: the columns built
+// in HBM (table.hip).  rows (device memory, null: the lines first + k): row k
+// is line rows[k].
+static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_col* cols, int n_cols) {
     if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-    if (first < 0 || count < 0 || first + count > h->n_lines || n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
+    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines) || n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
+    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
     auto ta = std::make_unique<lp::TableArgs>();
     memset(ta.get(), 0, sizeof(lp::TableArgs));
     ta->first = first;
     ta->count = count;
     ta->n_cols = n_cols;
+    ta->rows = rows;
+    ta->n_lines = h->n_lines;
+    ta->first_line = h->first_line;
     std::string names;
     for (int c = 0; c < n_cols; ++c) {
         lp_table_col& C = cols[c];
@@ -1103,9 +1126,12 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, lp_table_col
     if (!h->targs.ensure(sizeof(lp::TableArgs))) return LP_E_NOMEM;
     int n_str = 0;
     for (int c = 0; c < n_cols; ++c) n_str += cols[c].kind == LP_CAST_STRING ? 1 : 0;
-    const size_t scratch = lp::table_scratch_bytes(count, n_str);
-    if (!h->tscratch.ensure(scratch)) return LP_E_NOMEM;
+    // (the row-list instances' flag word: 256 bytes after the value words)
+    const size_t scratch = lp::table_scratch_bytes(count, n_str), flag_at = (scratch + 255) & ~(size_t)255;
+    if (!h->tscratch.ensure(flag_at + 256)) return LP_E_NOMEM;
     ta->srcw = reinterpret_cast<uint64_t*>((char*)h->tscratch.p + lp::table_srcw_offset(count));
+    ta->bad_row = reinterpret_cast<uint32_t*>((char*)h->tscratch.p + flag_at);
+    const bool ext = lp::table_ext(*ta) && count > 0;
     if (hipMemcpyAsync(h->targs.p, ta.get(), sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess) return LP_E_DEVICE;
     const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
     const lp::TableArgs* d_targs = h->targs.as<lp::TableArgs>();
@@ -1119,7 +1145,10 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, lp_table_col
         if (cols[c].kind == LP_CAST_STRING &&
             hipMemcpyAsync(&tot[c], cols[c].i64 + count, 8, hipMemcpyDeviceToHost, s) != hipSuccess)
             return LP_E_DEVICE;
+    uint32_t bad_row = 0;  // a rows[k] outside the batch (its row: valid 0)
+    if (ext && hipMemcpyAsync(&bad_row, ta->bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
     if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+    if (bad_row) return LP_E_INVALID;
     bool fits = true;
     for (int c = 0; c < n_cols; ++c) {
         if (cols[c].kind != LP_CAST_STRING) continue;
@@ -1140,8 +1169,10 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, lp_table_col
     return LP_OK;
 }
 
-int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_col* cols, int n_cols,
-                    int threads) {
+// lp_result_table (rows null: row k = line first + k) and lp_result_table_rows
+// (row k = line rows[k], first 0, count = n_rows)
+static int table_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                     lp_table_col* cols, int n_cols, int threads) {
     if (!h || !r || !cols || n_cols <= 0) return LP_E_INVALID;
     for (int c = 0; c < n_cols; ++c) {  // the same validation in both modes
         const lp_table_col& C = cols[c];
@@ -1149,6 +1180,10 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
             return LP_E_INVALID;
         if (C.kind != LP_CAST_STRING && C.kind != LP_CAST_LONG && C.kind != LP_CAST_DOUBLE) return LP_E_INVALID;
         std::string p = C.path;
+        if (const int pk = lp::Plan::pseudo_kind(p)) {  // a pseudo-column: no dissector, no casts entry
+            if (C.kind != (pk == lp::TC_LINE ? LP_CAST_STRING : LP_CAST_LONG)) return LP_E_INVALID;
+            continue;
+        }
         int casts = h->plan.casts(p);
         if (casts < 0) {
             const size_t dot = p.rfind('.');
@@ -1162,11 +1197,15 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
         if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
             r->line_off != h->line_off.as<uint64_t>())
             return LP_E_STATE;
-        return table_device(h, first, count, cols, n_cols);
+        return table_device(h, first, count, rows, cols, n_cols);
     }
     if (!r->input) return LP_E_INVALID;
-    if (first < 0 || count < 0 || first + count > r->n_lines) return LP_E_INVALID;
+    if (first < 0 || count < 0 || (!rows && first + count > r->n_lines)) return LP_E_INVALID;
+    if (rows)  // every index inside the batch, before anything is written
+        for (int64_t k = 0; k < count; ++k)
+            if (rows[k] < 0 || rows[k] >= r->n_lines) return LP_E_INVALID;
     std::unordered_map<std::string, std::vector<int>> by_path;
+    std::vector<int> pseudo(n_cols, 0);  // per column: its TC_* kind when it is a pseudo-column
     for (int c = 0; c < n_cols; ++c) {
         const lp_table_col& C = cols[c];
         if (!C.path || !C.valid || (C.kind == LP_CAST_STRING ? !C.i64 : C.kind == LP_CAST_LONG ? !C.i64 : !C.f64))
@@ -1175,6 +1214,7 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
         // the casts of the requested path (or of its wildcard request) must
         // allow the column type: else the reference's store finds no setter
         std::string p = C.path;
+        if ((pseudo[c] = lp::Plan::pseudo_kind(p))) continue;  // (its kind was checked above)
         int casts = h->plan.casts(p);
         if (casts < 0) {
             const size_t dot = p.rfind('.');
@@ -1196,7 +1236,25 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
         TableCtx ctx{&by_path, cols, 0, &sbuf[t], &sref[t], a};
         for (int64_t k = a; k < b; ++k) {
             for (int c = 0; c < n_cols; ++c) cols[c].valid[k] = 0;
-            const int64_t i = first + k;
+            const int64_t i = rows ? rows[k] : first + k;
+            // the pseudo-columns, from the copied line index and status: every row has them
+            for (int c = 0; c < n_cols; ++c) {
+                if (!pseudo[c]) continue;
+                lp_table_col& C = cols[c];
+                if (pseudo[c] == lp::TC_LINE) {  // the line as the parse kernels see it (kernels_common.h crlf_len)
+                    const uint64_t s0 = V.line_off[i];
+                    uint64_t n = V.line_off[i + 1] - 1 - s0;
+                    if (n > 0 && V.input[s0 + n - 1] == '\r') --n;
+                    std::string& buf = sbuf[t][c];
+                    sref[t][c][(size_t)(k - a)] = {(uint64_t)buf.size(), (uint32_t)n};
+                    buf.append((const char*)V.input + s0, (size_t)n);
+                } else {
+                    C.i64[k] = pseudo[c] == lp::TC_OFFSET ? (int64_t)V.line_off[i]
+                               : pseudo[c] == lp::TC_LINENO ? r->first_line + i
+                                                            : (int64_t)(V.status ? V.status[i] : LP_LINE_FALLBACK);
+                }
+                C.valid[k] = 1;
+            }
             if (!V.status || V.status[i] != LP_LINE_OK) continue;
             ctx.row = k;
             h->plan.rec_row(V, i, table_value, &ctx);
@@ -1229,6 +1287,17 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
         C.i64[count] = (int64_t)pos;
     }
     return rc;
+}
+
+int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_col* cols, int n_cols,
+                    int threads) {
+    return table_any(h, r, first, count, nullptr, cols, n_cols, threads);
+}
+
+int lp_result_table_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows, lp_table_col* cols,
+                         int n_cols, int threads) {
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
+    return table_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
 }
 
 // ---- wildcard targets as map columns (ParsedRecord.setMultiValueString)
@@ -1265,10 +1334,13 @@ void map_member(void* vctx, const std::string& wildcard, const std::string& key,
 }
 }  // namespace
 
-// lp_result_table_map on a device view: the columns built in HBM (table.hip)
-static int table_map_device(lp_handle* h, int64_t first, int64_t count, lp_table_map_col* cols, int n_cols) {
+// lp_result_table_map / lp_result_table_map_rows on a device view: the columns
+// built in HBM (table.hip).  rows as table_device's.
+static int table_map_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_map_col* cols,
+                            int n_cols) {
     if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-    if (first < 0 || count < 0 || first + count > h->n_lines) return LP_E_INVALID;
+    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines)) return LP_E_INVALID;
+    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
     std::vector<lp::MapArgs> args((size_t)n_cols);
     for (int c = 0; c < n_cols; ++c) {
         lp::MapArgs& M = args[(size_t)c];
@@ -1276,6 +1348,8 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, lp_table
         if (!h->plan.table_map_src(cols[c].path, M.src)) return LP_E_UNSUPPORTED;
         M.first = first;
         M.count = count;
+        M.rows = rows;
+        M.n_lines = h->n_lines;
         M.valid = cols[c].valid;
         M.entry_off = cols[c].entry_off;
         M.key_off = cols[c].key_off;
@@ -1300,7 +1374,10 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, lp_table
         if (lp::launch_map_count(d_args, M, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0) return LP_E_DEVICE;
         hipEventRecord(h->mev[1], s);
         if (hipMemcpyAsync(&pieces, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        uint32_t bad_row = 0;  // a rows[k] outside the batch (its row: valid 0, no entries)
+        if (rows && hipMemcpyAsync(&bad_row, M.bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        if (bad_row) return LP_E_INVALID;
         float t = 0;
         hipEventElapsedTime(&t, h->mev[0], h->mev[1]);
         ms[0] += t;
@@ -1351,8 +1428,10 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, lp_table
     return rc;
 }
 
-int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_map_col* cols, int n_cols,
-                        int threads) {
+// lp_result_table_map (rows null: row k = line first + k) and
+// lp_result_table_map_rows (row k = line rows[k], first 0, count = n_rows)
+static int table_map_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                         lp_table_map_col* cols, int n_cols, int threads) {
     if (!h || !r || !cols || n_cols <= 0) return LP_E_INVALID;
     std::unordered_map<std::string, std::vector<int>> by_path;
     for (int c = 0; c < n_cols; ++c) {  // the same validation in both modes
@@ -1370,10 +1449,13 @@ int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t
         if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
             r->line_off != h->line_off.as<uint64_t>())
             return LP_E_STATE;
-        return table_map_device(h, first, count, cols, n_cols);
+        return table_map_device(h, first, count, rows, cols, n_cols);
     }
     if (!r->input) return LP_E_INVALID;
-    if (first < 0 || count < 0 || first + count > r->n_lines) return LP_E_INVALID;
+    if (first < 0 || count < 0 || (!rows && first + count > r->n_lines)) return LP_E_INVALID;
+    if (rows)  // every index inside the batch, before anything is written
+        for (int64_t k = 0; k < count; ++k)
+            if (rows[k] < 0 || rows[k] >= r->n_lines) return LP_E_INVALID;
     lp::ResultView V;
     make_view(h, *r, V);
     const int T = std::max(1, std::min(threads > 0 ? threads : 1, 64));
@@ -1386,7 +1468,7 @@ int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t
         MapRowCtx ctx{&by_path, &items, &last};
         for (int c = 0; c < n_cols; ++c) chunk[t][c].per_row.assign((size_t)(b - a), 0u);
         for (int64_t k = a; k < b; ++k) {
-            const int64_t i = first + k;
+            const int64_t i = rows ? rows[k] : first + k;
             const bool ok = V.status && V.status[i] == LP_LINE_OK;
             for (int c = 0; c < n_cols; ++c) cols[c].valid[k] = ok ? 1 : 0;  // an OK line's record exists: its map may be empty
             if (!ok) continue;
@@ -1456,6 +1538,70 @@ int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t
         C.val_off[e] = (int64_t)vpos;
     }
     return rc;
+}
+
+int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_map_col* cols, int n_cols,
+                        int threads) {
+    return table_map_any(h, r, first, count, nullptr, cols, n_cols, threads);
+}
+
+int lp_result_table_map_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows, lp_table_map_col* cols,
+                             int n_cols, int threads) {
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
+    return table_map_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
+}
+
+// The lines of a window whose status is in status_mask, ascending (select.hip on
+// a device view; a loop over the copied status column on a host copy)
+int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask, int64_t* rows,
+                     uint64_t rows_cap, uint64_t* rows_len) {
+    if (!h || !r || !rows_len) return LP_E_INVALID;
+    if (status_mask & ~(uint32_t)(LP_SEL_OK | LP_SEL_BAD | LP_SEL_FALLBACK)) return LP_E_INVALID;
+    *rows_len = 0;
+    if (!r->on_host) {
+        // a device view is only good for the batch the handle holds now
+        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
+            r->line_off != h->line_off.as<uint64_t>())
+            return LP_E_STATE;
+        if (ensure_synced(h) != LP_OK) return LP_E_STATE;
+        if (first < 0 || count < 0 || first + count > h->n_lines) return LP_E_INVALID;
+        if (rows_cap && !device_memory(h, rows)) return LP_E_INVALID;
+        if (count == 0 || status_mask == 0) return LP_OK;
+        hipSetDevice(h->device);
+        hipStream_t s = h->stream;
+        if (!h->tscratch.ensure(lp::select_scratch_bytes(first, count))) return LP_E_NOMEM;
+        const int64_t* d_total = nullptr;
+        int64_t total = 0;
+        hipEventRecord(h->sev[0], s);
+        if (lp::launch_select_count(h->C.status, first, count, status_mask, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0)
+            return LP_E_DEVICE;
+        // the number of selected lines decides whether they fit
+        if (hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        *rows_len = (uint64_t)total;
+        if ((uint64_t)total > rows_cap) return LP_E_NOMEM;
+        if (total > 0 &&
+            lp::launch_select_write(h->C.status, first, count, status_mask, rows, h->tscratch.p, h->tscratch.cap, s) != 0)
+            return LP_E_DEVICE;
+        hipEventRecord(h->sev[1], s);
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        // (the host's read of the total between the passes is inside the interval)
+        hipEventElapsedTime(&h->sel_ms, h->sev[0], h->sev[1]);
+        return LP_OK;
+    }
+    if (first < 0 || count < 0 || first + count > r->n_lines) return LP_E_INVALID;
+    lp::ResultView V;
+    make_view(h, *r, V);
+    if (!V.status && count > 0) return LP_E_INVALID;
+    auto selected = [&](int64_t i) { return ((status_mask >> (V.status[i] & 7u)) & 1u) != 0; };
+    uint64_t n = 0;
+    for (int64_t i = first; i < first + count; ++i) n += selected(i) ? 1 : 0;
+    *rows_len = n;
+    if (n > rows_cap || (n && !rows)) return LP_E_NOMEM;  // (nothing written)
+    n = 0;
+    for (int64_t i = first; i < first + count; ++i)
+        if (selected(i)) rows[n++] = i;
+    return LP_OK;
 }
 
 int lp_result_emit(lp_handle* h, const lp_result* r, int64_t i, lp_emit_fn fn, void* ctx) {

@@ -108,6 +108,10 @@ int launch_histograms(const DeviceArgs* d_args, const uint8_t* buf, int64_t cap_
 size_t table_scratch_bytes(int64_t count, int n_str);
 // where TableArgs::srcw starts in that scratch
 size_t table_srcw_offset(int64_t count);
+// the table runs the kernels' row-list instances (a row list or a pseudo-column,
+// lp_table.h): ta.bad_row is then zeroed by launch_table_values and read by the
+// caller with the STRING totals
+bool table_ext(const TableArgs& ta);
 // mid (optional): recorded after k_table_values, before the offset scans
 int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
                         void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid = nullptr);
@@ -125,11 +129,29 @@ int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const
 //                      of the entry count (u32), key bytes and value bytes
 //   launch_map_fill    (the totals fit the caller's buffers) offsets and bytes
 // Each binds ma's scratch pointers itself.
+// With ma.rows set (lp_result_table_map_rows) launch_map_count zeroes and binds
+// ma.bad_row (a device word: a row index outside the batch), which the caller
+// reads with the piece total.
 size_t map_scratch_bytes(int64_t count, int64_t pieces);
 int launch_map_count(const DeviceArgs* d_args, MapArgs& ma, void* scratch, size_t scratch_bytes, hipStream_t s,
                      const int64_t** total);
 int launch_map_entries(const DeviceArgs* d_args, MapArgs& ma, const uint8_t* buf, void* scratch, size_t scratch_bytes,
                        hipStream_t s, const void* totals[3]);
 int launch_map_fill(MapArgs& ma, int64_t n_entries, void* scratch, size_t scratch_bytes, hipStream_t s);
+
+// lp_result_select on a device view (select.hip): the lines of [first, first +
+// count) (count > 0) whose status is in mask, ascending, as int64 line indices.
+// One lane takes 16 lines, one wave SEL_WAVE_LINES, one block SEL_BLOCK_LINES
+// (counted from first rounded down to 16).
+//   launch_select_count  the blocks' match counts and their scan; *total: the
+//                        device word that will hold the number of matches
+//   launch_select_write  (the total fits rows) the indices
+constexpr int SEL_WAVE_LINES = 1024;
+constexpr int SEL_BLOCK_LINES = 4096;
+size_t select_scratch_bytes(int64_t first, int64_t count);
+int launch_select_count(const uint8_t* status, int64_t first, int64_t count, uint32_t mask, void* scratch,
+                        size_t scratch_bytes, hipStream_t s, const int64_t** total);
+int launch_select_write(const uint8_t* status, int64_t first, int64_t count, uint32_t mask, int64_t* rows, void* scratch,
+                        size_t scratch_bytes, hipStream_t s);
 
 }  // namespace lp

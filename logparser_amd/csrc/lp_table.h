@@ -30,7 +30,15 @@ enum : int32_t {
     TC_PAIR,       // a = pair stage (cookie / raw query), b / c = offset / length of the name in TableArgs::names (the last occurrence)
     TC_SETC,       // a = Set-Cookie pair stage | SC_* field << 8, b / c = the cookie name in TableArgs::names:
                    // ResponseSetCookieDissector on the name's last cookie string
+    // the pseudo-columns ("@line" / "@offset" / "@lineno" / "@status"): what the record reader knows of a
+    // line without dissecting it (ApacheHttpdLogfileRecordReader.java:246-287: the line's text, its
+    // LongWritable key), valid for every row whatever its status; the same for every LogFormat
+    TC_LINE,       // STRING: the line's bytes [line_off[i], line_off[i + 1] - 1) less the '\r' of "\r\n"
+    TC_OFFSET,     // LONG: line_off[i]
+    TC_LINENO,     // LONG: TableArgs::first_line + i
+    TC_STATUS,     // LONG: status[i]
 };
+constexpr bool tc_pseudo(int32_t kind) { return kind >= TC_LINE && kind <= TC_STATUS; }
 // ResponseSetCookieDissector outputs (dissectors/ResponseSetCookieDissector.java:49-58)
 enum : int32_t { SC_VALUE, SC_EXPIRES_S /* STRING:expires, seconds */, SC_EXPIRES_MS /* TIME.EPOCH:expires */,
                  SC_DOMAIN, SC_COMMENT, SC_PATH };
@@ -70,6 +78,13 @@ struct TableArgs {
     int64_t first, count;
     int32_t n_cols, pad;
     LP_G uint64_t* srcw;  // [STRING column rank][count] value words (scratch)
+    // row k is line rows[k] (lp_result_table_rows; null: line first + k).  An
+    // index outside [0, n_lines) is never dereferenced: the row is valid 0 and
+    // *bad_row is set (zeroed before the launch).  Read by the kernels'
+    // row-list instances only (table.hip), which also serve the pseudo-columns.
+    const LP_G int64_t* rows;
+    LP_G uint32_t* bad_row;
+    int64_t n_lines, first_line;  // the batch's line count; lp_result.first_line (TC_LINENO)
     TableCol cols[MAX_TABLE_COLS];
     uint8_t names[TABLE_NAMES];
 };
@@ -91,6 +106,9 @@ struct MapSrc {
 // same per entry (they reuse klen / vlen, dead after the scans).
 struct MapArgs {
     int64_t first, count, n_pieces;
+    const LP_G int64_t* rows;  // row k is line rows[k] (lp_result_table_map_rows; null: line first + k)
+    LP_G uint32_t* bad_row;    // set when a rows[k] is outside [0, n_lines) (such a row: valid 0, no pieces)
+    int64_t n_lines;
     MapSrc src[MAX_FMT];
     LP_G uint8_t* valid;
     LP_G int64_t *entry_off, *key_off, *val_off;

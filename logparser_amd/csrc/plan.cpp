@@ -1114,7 +1114,19 @@ int Plan::casts_of(const Dissector& d, const std::string& otype, const std::stri
     (void)otype;
 }
 
+int Plan::pseudo_kind(const std::string& path) {
+    return path == "@line" ? TC_LINE : path == "@offset" ? TC_OFFSET : path == "@lineno" ? TC_LINENO
+                                                       : path == "@status" ? TC_STATUS : 0;
+}
+
 bool Plan::table_src(const std::string& path, TableSrc out[MAX_FMT], std::string& names, TableSrc* alt) const {
+    if (const int pk = pseudo_kind(path)) {  // what the line index and the status column hold: no dissector involved
+        if (!device_ok_) return false;       // (no device program: the kernels' arguments are not on the device)
+        for (int f = 0; f < MAX_FMT; ++f) out[f] = TableSrc{pk, 0, 0, 0};
+        if (alt)
+            for (int f = 0; f < MAX_FMT; ++f) alt[f] = TableSrc{TC_NONE, 0, 0, 0};
+        return true;
+    }
     const size_t colon = path.find(':');
     if (colon == std::string::npos || !device_ok_) return false;
     const std::string type = path.substr(0, colon), name = path.substr(colon + 1);

@@ -166,7 +166,11 @@ public:
     // value in the host replay only
     // alt (optional): per LogFormat the earlier delivery used when out's
     // delivers no value (TC_NONE: none)
+    // The pseudo-columns "@line" / "@offset" / "@lineno" / "@status" (no ':': not a
+    // "TYPE:path") are answered for every LogFormat alike (TC_LINE..TC_STATUS).
     bool table_src(const std::string& path, TableSrc out[MAX_FMT], std::string& names, TableSrc* alt = nullptr) const;
+    // the TC_* kind of a pseudo-column's path (0: not one)
+    static int pseudo_kind(const std::string& path);
     // where the device table finds the members of a requested wildcard
     // "TYPE:prefix.*" (lp_table.h MapSrc), per LogFormat: the query stage or
     // the pair stage (PK_COOKIE / PK_QUERY / PK_SETC: the value is the piece's

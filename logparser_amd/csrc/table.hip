@@ -14,6 +14,14 @@
 //                   bytes of those rows, written 4-byte word by word
 //
 // What each source delivers mirrors Plan::replay (plan.cpp) case by case.
+//
+// Row lists (lp_result_table_rows / lp_result_table_map_rows: the dense
+// tables of the lines a record reader keeps, ApacheHttpdLogfileRecordReader.java:
+// 246-287, ApacheHttpdlogDeserializer.java:284-291): the kernels that turn a row
+// into a line have a second instance (EXT) that takes the line from
+// TableArgs::rows / MapArgs::rows, bound-checked, and evaluates the
+// pseudo-columns (lp_table.h TC_LINE..TC_STATUS).  The contiguous instances
+// are the code they were before the row lists.
 #include <hip/hip_runtime.h>
 
 #define LP_KERNEL_TU 1  // device column pointers are global-memory pointers (lp_program.h)
@@ -387,6 +395,18 @@ __device__ __forceinline__ bool row_view(const Program& P, const Columns& C, con
     return true;
 }
 
+// Row k's line of a row-list instance: rows[k] (null: first + k); false when
+// it is outside the batch (never dereferenced: *bad_row is set, every lane
+// that finds one stores the same 1)
+__device__ __forceinline__ bool row_line(const LP_G int64_t* rows, int64_t first, int64_t n_lines, LP_G uint32_t* bad_row,
+                                         int64_t k, int64_t& i) {
+    i = rows ? rows[k] : first + k;
+    if ((uint64_t)i < (uint64_t)n_lines) return true;
+    *bad_row = 1u;
+    return false;
+}
+
+template <bool EXT>
 __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restrict__ args,
                                                      const TableArgs* __restrict__ targs, const uint8_t* buf) {
     const Program& P = args->prog;
@@ -394,9 +414,11 @@ __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restric
     const TableArgs& T = *targs;
     const int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x;
     if (k >= T.count) return;
-    const int64_t i = T.first + k;
+    int64_t i = T.first + k;
+    bool in_batch = true;
+    if constexpr (EXT) in_batch = row_line(T.rows, T.first, T.n_lines, T.bad_row, k, i);
     const LP_G uint8_t *line = nullptr, *region = nullptr;
-    const bool ok = row_view(P, C, buf, i, line, region);
+    const bool ok = in_batch && row_view(P, C, buf, i, line, region);
     const int fmt = ok && P.n_fmt > 1 ? (int)C.fmt_id[i] : 0;
     for (int c = 0, rank = 0; c < T.n_cols; ++c) {
         const TableCol& col = T.cols[c];
@@ -404,6 +426,24 @@ __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restric
         int64_t x = 0;
         double d = 0.0;
         uint64_t w = 0;
+        if constexpr (EXT) {
+            // a pseudo-column: before the status test, valid for every row of the batch
+            const int32_t pk = col.src[0].kind;
+            if (in_batch && tc_pseudo(pk)) {
+                if (pk == TC_LINE) {  // the parse kernels' line: wave_lines' end, crlf_len
+                    const uint64_t s0 = C.line_off[i], e0 = C.line_off[i + 1] - 1;
+                    const LP_G uint8_t* lp = (const LP_G uint8_t*)buf + s0;
+                    uint64_t n = e0 - s0;
+                    if (n > 0 && lp[n - 1] == '\r') --n;
+                    x = (int64_t)n;
+                    w = (uint64_t)(uintptr_t)lp;
+                    valid = col.kind == 1;
+                } else {
+                    x = pk == TC_OFFSET ? (int64_t)C.line_off[i] : pk == TC_LINENO ? T.first_line + i : (int64_t)C.status[i];
+                    valid = col.kind == 2;
+                }
+            }
+        }
         // the later delivery, then (a value that is none for the column) the earlier
         for (int pass = 0; pass < 2 && ok && !valid; ++pass) {
             const TableSrc& sc = pass ? col.alt[fmt] : col.src[fmt];
@@ -456,6 +496,7 @@ __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restric
 constexpr int CW = 4;    // waves per block
 constexpr int FMTB = 24; // scratch bytes per row (a long's 20 characters at most)
 
+template <bool EXT>
 __global__ __launch_bounds__(64 * CW) void k_table_chars(const DeviceArgs* __restrict__ args,
                                                          const TableArgs* __restrict__ targs, const uint8_t* buf) {
     const Program& P = args->prog;
@@ -495,10 +536,13 @@ __global__ __launch_bounds__(64 * CW) void k_table_chars(const DeviceArgs* __res
             v.l = (int64_t)(w << 2) >> 2;
         } else {
             const LP_G uint8_t *line = nullptr, *region = nullptr;
-            if (row_view(P, C, buf, T.first + k, line, region)) {
-                const int fmt = P.n_fmt > 1 ? (int)C.fmt_id[T.first + k] : 0;
-                v = tvalue(P, C, T, col.src[fmt], T.first + k, line, region);
-                if (v.kind == 0) v = tvalue(P, C, T, col.alt[fmt], T.first + k, line, region);  // the earlier delivery
+            int64_t i = T.first + k;
+            bool in_batch = true;  // (a valid row's line is inside the batch: k_table_values checked it)
+            if constexpr (EXT) in_batch = row_line(T.rows, T.first, T.n_lines, T.bad_row, k, i);
+            if (in_batch && row_view(P, C, buf, i, line, region)) {
+                const int fmt = P.n_fmt > 1 ? (int)C.fmt_id[i] : 0;
+                v = tvalue(P, C, T, col.src[fmt], i, line, region);
+                if (v.kind == 0) v = tvalue(P, C, T, col.alt[fmt], i, line, region);  // the earlier delivery
             }
         }
         if (v.kind == 2) {
@@ -619,14 +663,17 @@ __device__ __forceinline__ const LP_G uint64_t* map_table(const Program& P, cons
     return nullptr;
 }
 
+template <bool EXT>
 __global__ __launch_bounds__(TB) void k_map_count(const DeviceArgs* __restrict__ args, const MapArgs M) {
     const Program& P = args->prog;
     const Columns& C = args->cols;
     const int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x;
     if (k > M.count) return;
     if (k == M.count) { M.cnt[k] = 0; return; }  // the scan's last item: the piece total
-    const int64_t i = M.first + k;
-    const bool ok = C.status[i] == ST_OK;
+    int64_t i = M.first + k;
+    bool in_batch = true;
+    if constexpr (EXT) in_batch = row_line(M.rows, M.first, M.n_lines, M.bad_row, k, i);
+    const bool ok = in_batch && C.status[i] == ST_OK;
     int64_t n = 0;
     if (ok) {
         const MapSrc s = M.src[P.n_fmt > 1 ? (int)C.fmt_id[i] : 0];
@@ -637,6 +684,7 @@ __global__ __launch_bounds__(TB) void k_map_count(const DeviceArgs* __restrict__
     M.cnt[k] = n;
 }
 
+template <bool EXT>
 __global__ __launch_bounds__(TB) void k_map_entries(const DeviceArgs* __restrict__ args, const MapArgs M,
                                                     const uint8_t* buf) {
     const Program& P = args->prog;
@@ -657,7 +705,8 @@ __global__ __launch_bounds__(TB) void k_map_entries(const DeviceArgs* __restrict
         if (M.pbase[mid] <= p) lo = mid;
         else hi = mid;
     }
-    const int64_t i = M.first + lo;
+    // (a row with pieces passed k_map_count's bound check: its line is inside the batch)
+    const int64_t i = EXT ? M.rows[lo] : M.first + lo;
     const uint32_t j = (uint32_t)(p - M.pbase[lo]), cnt = (uint32_t)(M.pbase[lo + 1] - M.pbase[lo]);
     const LP_G uint8_t *line = nullptr, *region = nullptr;
     row_view(P, C, buf, i, line, region);  // (a row with pieces is OK)
@@ -786,6 +835,14 @@ size_t table_scratch_bytes(int64_t count, int n_str) {
     return table_srcw_offset(count) + 8 * (size_t)count * (size_t)n_str + 256;
 }
 
+// the row-list instances: a row list, or a pseudo-column (the same for every LogFormat)
+bool table_ext(const TableArgs& ta) {
+    if (ta.rows) return true;
+    for (int c = 0; c < ta.n_cols; ++c)
+        if (tc_pseudo(ta.cols[c].src[0].kind)) return true;
+    return false;
+}
+
 int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
                         void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid) {
     if (ta.count > 0x7FFFFFFF) return -1;  // the scan's item count is an int
@@ -795,7 +852,12 @@ int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, cons
             if (ta.cols[c].kind == 1 && hipMemsetAsync(ta.cols[c].i64, 0, 8, s) != hipSuccess) return -1;
         return 0;
     }
-    hipLaunchKernelGGL(k_table_values, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+    if (table_ext(ta)) {
+        if (hipMemsetAsync(ta.bad_row, 0, 4, s) != hipSuccess) return -1;
+        hipLaunchKernelGGL(k_table_values<true>, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+    } else {
+        hipLaunchKernelGGL(k_table_values<false>, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+    }
     if (mid) hipEventRecord(mid, s);  // the values kernel done: the scans follow
     size_t tmp = 0;
     hipcub::DeviceScan::InclusiveSum(nullptr, tmp, (const int64_t*)nullptr, (int64_t*)nullptr, (int)n);
@@ -818,8 +880,9 @@ int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const
     for (int c = 0; c < ta.n_cols; ++c) n_str += ta.cols[c].kind == 1 ? 1 : 0;
     if (ta.count == 0 || n_str == 0) return 0;
     const int64_t waves = (ta.count + 63) / 64;
-    hipLaunchKernelGGL(k_table_chars, dim3((unsigned)((waves + CW - 1) / CW), (unsigned)n_str), dim3(64 * CW), 0, s,
-                       d_args, d_targs, buf);
+    const dim3 grid((unsigned)((waves + CW - 1) / CW), (unsigned)n_str);
+    if (ta.rows) hipLaunchKernelGGL(k_table_chars<true>, grid, dim3(64 * CW), 0, s, d_args, d_targs, buf);
+    else hipLaunchKernelGGL(k_table_chars<false>, grid, dim3(64 * CW), 0, s, d_args, d_targs, buf);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -828,7 +891,7 @@ int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const
 // second layout with the piece count known.
 namespace {
 struct MapLayout {
-    size_t cnt, pbase, tmp, tmp_bytes, flag, eidx, klen, vlen, kpos, vpos, ksrc, vsrc, total;
+    size_t cnt, pbase, bad_row, tmp, tmp_bytes, flag, eidx, klen, vlen, kpos, vpos, ksrc, vsrc, total;
 };
 MapLayout map_layout(int64_t count, int64_t pieces) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -838,6 +901,7 @@ MapLayout map_layout(int64_t count, int64_t pieces) {
     const size_t rows = (size_t)count + 1, pcs = (size_t)pieces + 1;
     L.cnt = take(8 * rows);
     L.pbase = take(8 * rows);
+    L.bad_row = take(4);
     size_t t1 = 0, t2 = 0, t3 = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, t1, (const int64_t*)nullptr, (int64_t*)nullptr, (int)rows);
     hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)pcs);
@@ -863,6 +927,7 @@ MapLayout map_bind(MapArgs& ma, void* scratch) {
     auto at = [&](auto& dst, size_t off) { dst = (std::remove_reference_t<decltype(dst)>)(b + off); };
     at(ma.cnt, L.cnt);
     at(ma.pbase, L.pbase);
+    at(ma.bad_row, L.bad_row);
     at(ma.flag, L.flag);
     at(ma.eidx, L.eidx);
     at(ma.klen, L.klen);
@@ -887,7 +952,12 @@ int launch_map_count(const DeviceArgs* d_args, MapArgs& ma, void* scratch, size_
     const MapLayout L = map_bind(ma, scratch);
     if (L.total > scratch_bytes) return -1;
     const int rows = (int)ma.count + 1;
-    hipLaunchKernelGGL(k_map_count, dim3(blocks_of(rows)), dim3(TB), 0, s, d_args, ma);
+    if (ma.rows) {
+        if (hipMemsetAsync(ma.bad_row, 0, 4, s) != hipSuccess) return -1;
+        hipLaunchKernelGGL(k_map_count<true>, dim3(blocks_of(rows)), dim3(TB), 0, s, d_args, ma);
+    } else {
+        hipLaunchKernelGGL(k_map_count<false>, dim3(blocks_of(rows)), dim3(TB), 0, s, d_args, ma);
+    }
     size_t t = L.tmp_bytes;
     if (hipcub::DeviceScan::ExclusiveSum((char*)scratch + L.tmp, t, (const int64_t*)ma.cnt, (int64_t*)ma.pbase, rows, s) !=
         hipSuccess)
@@ -902,7 +972,8 @@ int launch_map_entries(const DeviceArgs* d_args, MapArgs& ma, const uint8_t* buf
     const MapLayout L = map_bind(ma, scratch);
     if (L.total > scratch_bytes) return -1;
     const int pcs = (int)ma.n_pieces + 1;
-    hipLaunchKernelGGL(k_map_entries, dim3(blocks_of(pcs)), dim3(TB), 0, s, d_args, ma, buf);
+    if (ma.rows) hipLaunchKernelGGL(k_map_entries<true>, dim3(blocks_of(pcs)), dim3(TB), 0, s, d_args, ma, buf);
+    else hipLaunchKernelGGL(k_map_entries<false>, dim3(blocks_of(pcs)), dim3(TB), 0, s, d_args, ma, buf);
     void* tmp = (char*)scratch + L.tmp;
     size_t t = L.tmp_bytes;
     if (hipcub::DeviceScan::ExclusiveSum(tmp, t, (const uint32_t*)ma.flag, (uint32_t*)ma.eidx, pcs, s) != hipSuccess) return -1;
