@@ -130,6 +130,10 @@ int64_t lp_possible_paths_remapped(const char *logformats, int max_depth, const 
                                   shapes (common, combined with every path requested) is parsed by
                                   that shape's instance of the chunk kernel, lp_counters out[11];
                                   0: by the instances per program class, as every other program */
+#define LP_OPT_DICT_HASH_BITS 8 /* tests: lp_result_table_dict on a device view keeps only this many low
+                                  bits of a value's hash for its home slot (1..32; 0 = default, all 64
+                                  bits): distinct values then collide, and a few hundred rows run the
+                                  probe and byte-compare paths.  The result does not depend on it */
 int lp_set_option(lp_handle *h, int option, int64_t value);
 
 /* Capacity for the coming batches: columns for max_lines lines and at least
@@ -209,7 +213,12 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * k_map_count and the piece-base scan, [9] k_map_entries and its scans, [10]
  * k_map_fill and k_map_chars; then [11] the last complete lp_result_select on
  * a device view: k_select_count, the block scan, the host's read of the count
- * and k_select_write.  Returns the number of values written. */
+ * and k_select_write; then the last complete lp_result_table_dict on a device
+ * view, summed over its columns: [12] k_table_values of the rows, [13] the
+ * table reset and k_dict_insert, [14] k_dict_mark, the rank scan and
+ * k_dict_index, [15] the dictionary's values (k_table_values, the offset scan
+ * and k_table_chars over the representatives).  Returns the number of values
+ * written (at most 16). */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -492,6 +501,64 @@ int lp_result_table_rows(lp_handle *h, const lp_result *r, const int64_t *rows, 
                          lp_table_col *cols, int n_cols, int threads);
 int lp_result_table_map_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
                              lp_table_map_col *cols, int n_cols, int threads);
+
+/* ---- Dictionary-encoded STRING columns (Arrow dictionary<int32, utf8>). ----
+ * A log table's bytes are almost all strings from small value sets (method,
+ * protocol, status, host, user agent, referer, path).  The consumers' string
+ * types all have a dictionary form -- Arrow's DictionaryArray, ORC's
+ * DICTIONARY_V2 string encoding, Parquet's RLE_DICTIONARY -- which takes a
+ * 4-byte index per row and each distinct value once.  These calls build that
+ * form directly: the plain column's bytes are never written.  The gain is the
+ * output's size for a repetitive column, not the call's time: on a device
+ * view it takes longer than lp_result_table of the same path, and a column of
+ * nearly all distinct values comes out larger too.
+ *
+ * path: any path lp_result_table accepts with kind LP_CAST_STRING on this
+ * view, "@line" included.  Rows as lp_result_table (first, count) /
+ * lp_result_table_rows (rows, n_rows).  Exactly:
+ *   valid[k]  byte for byte what lp_result_table writes for the path as a
+ *             STRING column over the same rows;
+ *   index[k]  for a valid row, the dictionary entry whose bytes equal that
+ *             plain column's value of row k; 0 for a row that is not valid
+ *             (a null contributes no entry; "" is a value and gets one);
+ *   dict_off  [dict_len + 1] Arrow offsets into dict_chars: entry j is
+ *             dict_chars[dict_off[j], dict_off[j + 1]).
+ * Entries are pairwise distinct and ordered by FIRST OCCURRENCE: entry j is
+ * the value whose first valid row comes j-th, counting the call's row index
+ * k (with a row list that repeats or runs backwards the order follows k, not
+ * the line number).  The result is therefore deterministic, and a host copy
+ * and a device view give identical index, dict_off and dict_chars.
+ * Sizes as chars_cap / chars_len: every call sets dict_len (distinct values
+ * among the valid rows) and dict_chars_len (their bytes); when dict_cap <
+ * dict_len or dict_chars_cap < dict_chars_len the call returns LP_E_NOMEM with
+ * both lengths exact, nothing is written past either capacity, and the other
+ * outputs are unspecified: call again.  dict_off has room for dict_cap + 1
+ * words and is never NULL.
+ * Errors: count (n_rows) above 2^31 - 1 is LP_E_INVALID; the others are those
+ * of lp_result_table / lp_result_table_rows (a row index outside the batch,
+ * LP_E_UNSUPPORTED for a path the device table does not derive,
+ * LP_E_MISSING).  On a device view every pointer and the row list are memory
+ * of the handle's device (anything else: LP_E_INVALID, nothing dereferenced),
+ * and the column is built in HBM by a lock-free hash kernel; on a
+ * host copy it is built from the host table and a hash map, `threads` as in
+ * lp_result_table.  LP_E_DEVICE if the device's hash table overflowed (it
+ * cannot: it has two slots per row).  lp_last_timing [12..15]: the last
+ * device call's phases, summed over its columns. */
+typedef struct lp_table_dict_col {
+    const char *path;
+    uint8_t *valid;          /* [count] */
+    int32_t *index;          /* [count] */
+    int64_t *dict_off;       /* [dict_cap + 1] */
+    char    *dict_chars;     /* dict_chars_cap bytes */
+    int64_t  dict_cap;       /* in:  entries dict_off has room for */
+    uint64_t dict_chars_cap; /* in */
+    int64_t  dict_len;       /* out: distinct values among the valid rows */
+    uint64_t dict_chars_len; /* out: bytes of the dictionary's values */
+} lp_table_dict_col;
+int lp_result_table_dict(lp_handle *h, const lp_result *r, int64_t first, int64_t count, lp_table_dict_col *cols,
+                         int n_cols, int threads);
+int lp_result_table_dict_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
+                              lp_table_dict_col *cols, int n_cols, int threads);
 
 /* Description of the compiled device program (for logs/tests), NUL-terminated. */
 int64_t lp_describe(lp_handle *h, char *out, size_t cap);

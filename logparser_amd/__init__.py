@@ -35,6 +35,7 @@ LINE_OK, LINE_BAD, LINE_FALLBACK = 0, 1, 2
 BUF_HOST, BUF_DEVICE = 0, 1
 OPT_FORCE_DIRECT, OPT_MAX_RETRIES, OPT_ARENA_BYTES, OPT_CHUNK_LINES, OPT_CHUNK_WAIT, OPT_ONE_PASS = 1, 2, 3, 4, 5, 6
 OPT_FIXED_SHAPE = 7  # 0: never the chunk kernel's fixed-shape instances (default 1)
+OPT_DICT_HASH_BITS = 8  # tests: low bits of a value's hash the device dictionary keeps for its home slot (0: all)
 ARENA_SHARDS = 64
 # lp_result_select's status mask (1 << LINE_*)
 SEL_OK, SEL_BAD, SEL_FALLBACK = 1 << LINE_OK, 1 << LINE_BAD, 1 << LINE_FALLBACK
@@ -68,6 +69,24 @@ class LpTableMapCol(ctypes.Structure):
                 ("val_chars", ctypes.c_void_p), ("entries_cap", ctypes.c_uint64), ("key_chars_cap", ctypes.c_uint64),
                 ("val_chars_cap", ctypes.c_uint64), ("entries_len", ctypes.c_uint64),
                 ("key_chars_len", ctypes.c_uint64), ("val_chars_len", ctypes.c_uint64)]
+
+
+class LpTableDictCol(ctypes.Structure):
+    """lp_table_dict_col (include/logparser_amd.h): one Arrow dictionary<int32, utf8> column"""
+    _fields_ = [("path", ctypes.c_char_p), ("valid", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("dict_off", ctypes.c_void_p), ("dict_chars", ctypes.c_void_p), ("dict_cap", ctypes.c_int64),
+                ("dict_chars_cap", ctypes.c_uint64), ("dict_len", ctypes.c_int64), ("dict_chars_len", ctypes.c_uint64)]
+
+
+def strings_from_dict(valid, index, dict_off, dict_chars):
+    """The rows of a dictionary-encoded STRING column (lp_result_table_dict) as
+    a list of str | None: row k is dictionary entry index[k] --
+    dict_chars[dict_off[j], dict_off[j + 1]) (UTF-8) -- or None where valid[k]
+    is 0."""
+    chars = bytes(bytearray(dict_chars))
+    off = [int(x) for x in dict_off]
+    entries = [chars[off[j]:off[j + 1]].decode("utf-8") for j in range(len(off) - 1)]
+    return [entries[int(i)] if v else None for v, i in zip(valid, index)]
 
 
 MAP_ARRAYS = ("valid", "entry_off", "key_off", "key_chars", "val_off", "val_chars")
@@ -194,6 +213,12 @@ def lib():
     L.lp_result_table_map_rows.restype = ctypes.c_int
     L.lp_result_table_map_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.POINTER(LpTableMapCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_table_dict.restype = ctypes.c_int
+    L.lp_result_table_dict.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.POINTER(LpTableDictCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_table_dict_rows.restype = ctypes.c_int
+    L.lp_result_table_dict_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.POINTER(LpTableDictCol), ctypes.c_int, ctypes.c_int]
     L.lp_casts.restype = ctypes.c_int
     L.lp_casts.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     L.lp_describe.restype = ctypes.c_int64
@@ -559,6 +584,101 @@ class BatchResult:
         t = (ctypes.c_float * 8)()
         lib().lp_last_timing(self._p._h, t, 8)
         return {"values": t[5], "scans": t[6], "chars": t[7]}
+
+    def _dict_call(self, res, paths, first, count, rows_p, threads, bufs, alloc, ptr):
+        """lp_result_table_dict / _rows into bufs (per path [valid, index,
+        dict_off, dict_chars]); after LP_E_NOMEM the dictionary's arrays are
+        replaced by ones of the reported sizes and the call repeated once"""
+        L = lib()
+        cols = (LpTableDictCol * len(paths))()
+        for k, path in enumerate(paths):
+            c = cols[k]
+            c.path = path.encode()
+            valid, index, doff, dchars = bufs[k]
+            c.valid, c.index, c.dict_off, c.dict_chars = ptr(valid), ptr(index), ptr(doff), ptr(dchars)
+            c.dict_cap, c.dict_chars_cap = len(doff) - 1, len(dchars)
+        call = (lambda: L.lp_result_table_dict(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)) \
+            if rows_p is None else \
+            (lambda: L.lp_result_table_dict_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(paths), threads))
+        rc = call()
+        if rc == LP_E_NOMEM:
+            for k in range(len(paths)):
+                c = cols[k]
+                if c.dict_len > c.dict_cap:
+                    bufs[k][2] = alloc(c.dict_len + 1, "int64")
+                    c.dict_off, c.dict_cap = ptr(bufs[k][2]), c.dict_len
+                if c.dict_chars_len > c.dict_chars_cap:
+                    bufs[k][3] = alloc(max(1, c.dict_chars_len), "uint8")
+                    c.dict_chars, c.dict_chars_cap = ptr(bufs[k][3]), len(bufs[k][3])
+            rc = call()
+        if rc == LP_E_UNSUPPORTED:
+            raise FallbackRequired("a column's values are derived on the host only: use table_dict_from")
+        if rc != LP_OK:
+            raise ValueError("lp_result_table_dict failed: %d" % rc)
+        return {path: (bufs[k][1][:count], (bufs[k][2][:cols[k].dict_len + 1], bufs[k][3][:cols[k].dict_chars_len]),
+                       bufs[k][0][:count]) for k, path in enumerate(paths)}
+
+    def table_dict_buffers(self, columns, count=None, dict_cap=None, dict_chars_cap=None, rows=None):
+        """Device buffers for table_dict_device(columns, buffers=...): per
+        path [valid uint8 [count], index int32 [count], dict_off int64
+        [dict_cap + 1], dict_chars uint8 [dict_chars_cap]]; rows: a row list
+        (room for that many rows)."""
+        import torch
+        if rows is not None:
+            if count is not None:
+                raise ValueError("rows excludes first / count")
+            count = int(rows.numel())
+        count = self.n_lines if count is None else count
+        dev = torch.device("cuda", self._p.device)
+        return [[torch.empty(max(1, count), dtype=torch.uint8, device=dev),
+                 torch.empty(max(1, count), dtype=torch.int32, device=dev),
+                 torch.empty((dict_cap or 0) + 1, dtype=torch.int64, device=dev),
+                 torch.empty(max(1, dict_chars_cap or 0), dtype=torch.uint8, device=dev)] for _ in columns]
+
+    def table_dict_device(self, columns, first=0, count=None, rows=None, buffers=None, dict_cap=None, dict_chars_cap=None):
+        """lp_result_table_dict on the device view: dictionary-encoded STRING
+        columns (Arrow dictionary<int32, utf8>) of rows [first, first+count)
+        -- or, with rows (a torch int64 tensor on the device; not together
+        with first / count), of exactly those lines -- built in HBM without
+        writing the plain column's bytes.  columns: paths (any path
+        table_device takes as str, "@line" included).  Returns {path: (index
+        int32 [count], (dict_off int64 [dict_len + 1], dict_chars uint8),
+        valid uint8 [count])} of torch tensors on the handle's device;
+        entries in the order of first occurrence.  dict_cap / dict_chars_cap:
+        room allotted per column (default: none, the call is repeated once
+        with the sizes the first reports); buffers: table_dict_buffers(...)."""
+        import torch
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, True)
+        count = self.n_lines - first if count is None else count
+        dev = torch.device("cuda", self._p.device)
+        dt = {"int64": torch.int64, "uint8": torch.uint8}
+        bufs = buffers if buffers is not None else self.table_dict_buffers(columns, count, dict_cap, dict_chars_cap)
+        return self._dict_call(self._view(), list(columns), first, count, rows_p, 0, bufs,
+                               lambda n, t: torch.empty(n, dtype=dt[t], device=dev), lambda a: a.data_ptr())
+
+    def table_dict_from(self, res, columns, first=0, count=None, threads=16, rows=None):
+        """lp_result_table_dict from a host copy: the same arrays as
+        table_dict_device, as numpy arrays (bit-identical to the device's)"""
+        rows_p = None
+        if rows is not None:
+            rows_p, count = self._rows_arg(rows, first, count, False)
+        count = self.n_lines - first if count is None else count
+        bufs = [[np.zeros(max(1, count), dtype=np.uint8), np.zeros(max(1, count), dtype=np.int32),
+                 np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.uint8)] for _ in columns]
+        for b in bufs:
+            b[3] = b[3][:0]
+        return self._dict_call(res, list(columns), first, count, rows_p, threads, bufs,
+                               lambda n, t: np.zeros(n, dtype=t), lambda a: a.ctypes.data)
+
+    def table_dict_timing(self):
+        """HIP-event ms of the last device lp_result_table_dict's phases, summed over its columns:
+        {"values": k_table_values of the rows, "insert": table reset + k_dict_insert,
+        "index": k_dict_mark + rank scan + k_dict_index, "dict": the dictionary's values}"""
+        t = (ctypes.c_float * 16)()
+        lib().lp_last_timing(self._p._h, t, 16)
+        return {"values": t[12], "insert": t[13], "index": t[14], "dict": t[15]}
 
     def _map_call(self, res, paths, first, count, threads, alloc, bufs, rows_p=None):
         """lp_result_table_map with lp_result_table's size protocol: a first

@@ -10,6 +10,7 @@
 #include <unordered_map>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "../../include/logparser_amd.h"
@@ -109,6 +110,9 @@ struct lp_handle {
     float mms[3] = {0, 0, 0};  // the last device lp_result_table_map's phases, summed over its columns
     hipEvent_t sev[2]{}; // device lp_result_select: start, end of its kernels
     float sel_ms = 0;    // the last device lp_result_select's count pass, scan and write pass
+    hipEvent_t dev_ev[5]{};  // device lp_result_table_dict: a column's start, rows' values, insert, index, dictionary values
+    float dms[4] = {0, 0, 0, 0};  // the last device lp_result_table_dict's phases, summed over its columns
+    int dict_hash_bits = 0;  // LP_OPT_DICT_HASH_BITS (tests: 0 = the whole hash)
     bool have_events = false;
     uint64_t counters[4]{};
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
@@ -668,6 +672,7 @@ lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths,
     for (auto& ev : h->tev) hipEventCreate(&ev);
     for (auto& ev : h->mev) hipEventCreate(&ev);
     for (auto& ev : h->sev) hipEventCreate(&ev);
+    for (auto& ev : h->dev_ev) hipEventCreate(&ev);
     h->have_events = true;
     if (!h->meta.ensure(sizeof(lp::Meta))) { if (status) *status = LP_E_NOMEM; return nullptr; }
     if (status) *status = st;
@@ -686,6 +691,7 @@ void lp_free(lp_handle* h) {
         for (auto& ev : h->tev) hipEventDestroy(ev);
         for (auto& ev : h->mev) hipEventDestroy(ev);
         for (auto& ev : h->sev) hipEventDestroy(ev);
+        for (auto& ev : h->dev_ev) hipEventDestroy(ev);
     }
     delete h;
 }
@@ -736,6 +742,10 @@ int lp_set_option(lp_handle* h, int option, int64_t value) {
     case LP_OPT_ARENA_BYTES:
         if (value < 0) return LP_E_INVALID;
         h->arena_first = (uint64_t)value;
+        return LP_OK;
+    case LP_OPT_DICT_HASH_BITS:
+        if (value < 0 || value > 32) return LP_E_INVALID;
+        h->dict_hash_bits = (int)value;
         return LP_OK;
     default: return LP_E_INVALID;
     }
@@ -906,7 +916,8 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     for (int k = 5; k < n && k < 8; ++k) out[k] = h->tms[k - 5];
     for (int k = 8; k < n && k < 11; ++k) out[k] = h->mms[k - 8];
     if (n > 11) out[11] = h->sel_ms;
-    return n < 12 ? n : 12;
+    for (int k = 12; k < n && k < 16; ++k) out[k] = h->dms[k - 12];
+    return n < 16 ? n : 16;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1159,6 +1170,11 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_
     if (lp::launch_table_chars(d_args, d_targs, *ta, h->d_buf, s) != 0) return LP_E_DEVICE;
     hipEventRecord(h->tev[3], s);
     if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+    // An empty table records no tev[1]: asking for its time left hipErrorInvalidHandle
+    // behind, which the next launch's hipGetLastError took for its own (the next
+    // lp_parse_batch on the handle then failed with LP_E_DEVICE).  So an empty call keeps
+    // the previous call's lp_last_timing [5..7].
+    if (count == 0) return LP_OK;
     float a = 0, b = 0, c = 0;
     hipEventElapsedTime(&a, h->tev[0], h->tev[1]);
     hipEventElapsedTime(&b, h->tev[1], h->tev[2]);
@@ -1298,6 +1314,234 @@ int lp_result_table_rows(lp_handle* h, const lp_result* r, const int64_t* rows, 
                          int n_cols, int threads) {
     if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
     return table_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
+}
+
+// ---- dictionary-encoded STRING columns (Arrow dictionary<int32, utf8>)
+
+// lp_result_table_dict / lp_result_table_dict_rows on a device view: one
+// column after the other in the same scratch (dict.hip; kernels.h DictLayout).
+// A column: k_table_values over the rows (validity, lengths, source words; no
+// offsets), the hash insert, the representatives' ranks and the indices, then
+// the dictionary's values as the STRING column of the representatives' lines
+// by the table's row-list instances.
+static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_dict_col* cols,
+                             int n_cols) {
+    if (ensure_synced(h) != LP_OK) return LP_E_STATE;
+    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines) || n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
+    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
+    for (int c = 0; c < n_cols; ++c) {  // every array the kernels write is memory of the device
+        const lp_table_dict_col& C = cols[c];
+        if (!device_memory(h, C.dict_off) || (count > 0 && (!device_memory(h, C.valid) || !device_memory(h, C.index))) ||
+            (C.dict_chars_cap > 0 && !device_memory(h, C.dict_chars)))
+            return LP_E_INVALID;
+    }
+    // every column's sources before anything is written
+    std::vector<std::unique_ptr<lp::TableArgs>> tas;
+    for (int c = 0; c < n_cols; ++c) {
+        auto ta = std::make_unique<lp::TableArgs>();
+        memset(ta.get(), 0, sizeof(lp::TableArgs));
+        ta->first = first;
+        ta->count = count;
+        ta->n_cols = 1;
+        ta->rows = rows;
+        ta->n_lines = h->n_lines;
+        ta->first_line = h->first_line;
+        std::string names;
+        lp::TableCol& T = ta->cols[0];
+        T.kind = LP_CAST_STRING;
+        if (!h->plan.table_src(cols[c].path, T.src, names, T.alt)) return LP_E_UNSUPPORTED;
+        if (names.size() > sizeof(ta->names)) return LP_E_UNSUPPORTED;
+        memcpy(ta->names, names.data(), names.size());
+        T.valid = cols[c].valid;
+        tas.push_back(std::move(ta));
+    }
+    hipSetDevice(h->device);
+    hipStream_t s = h->stream;
+    if (!h->targs.ensure(sizeof(lp::TableArgs))) return LP_E_NOMEM;
+    const lp::DictLayout L = lp::dict_layout(count);
+    if (!h->tscratch.ensure(L.total)) return LP_E_NOMEM;
+    void* const scratch = h->tscratch.p;
+    const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
+    const lp::TableArgs* d_targs = h->targs.as<lp::TableArgs>();
+    float ms[4] = {0, 0, 0, 0};
+    int rc = LP_OK;
+    for (int c = 0; c < n_cols; ++c) {
+        lp_table_dict_col& C = cols[c];
+        C.dict_len = 0;
+        C.dict_chars_len = 0;
+        if (count == 0) {  // an empty dictionary: its one offset
+            if (hipMemsetAsync(C.dict_off, 0, 8, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+            continue;
+        }
+        lp::TableArgs& ta = *tas[c];
+        lp::DictArgs da{};
+        da.count = count;
+        da.hash_bits = h->dict_hash_bits;
+        da.valid = C.valid;
+        da.index = C.index;
+        lp::dict_bind(da, ta, L, scratch);
+        const bool ext = lp::table_ext(ta);
+        if (hipMemcpyAsync(h->targs.p, &ta, sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess) return LP_E_DEVICE;
+        hipEventRecord(h->dev_ev[0], s);
+        if (lp::launch_table_values(d_args, d_targs, ta, h->d_buf, scratch, L.table_bytes, s, nullptr, false) != 0)
+            return LP_E_DEVICE;
+        hipEventRecord(h->dev_ev[1], s);
+        if (lp::launch_dict_insert(d_args, d_targs, ta, da, h->d_buf, s) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->dev_ev[2], s);
+        const uint32_t* d_total = nullptr;
+        if (lp::launch_dict_rank(da, L, scratch, s, &d_total) != 0 || lp::launch_dict_index(ta, da, s) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->dev_ev[3], s);
+        uint32_t total = 0, fail = 0, bad_row = 0;
+        if (hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(&fail, da.fail, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (ext && hipMemcpyAsync(&bad_row, ta.bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess))
+            return LP_E_DEVICE;
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        if (bad_row) return LP_E_INVALID;  // a rows[k] outside the batch
+        if (fail) return LP_E_DEVICE;      // a probe ran out of slots
+        C.dict_len = (int64_t)total;
+        const bool entries_fit = C.dict_len <= C.dict_cap;
+        // the dictionary's values: the STRING column of the representatives' lines (the
+        // offsets into scratch when dict_off has no room: the byte total is wanted all the same)
+        lp::TableArgs tv = ta;
+        tv.first = 0;
+        tv.count = C.dict_len;
+        tv.rows = da.reps;
+        tv.cols[0].valid = reinterpret_cast<uint8_t*>(da.slot);  // k_table_values writes 1 for every representative; k_table_chars reads them back
+        tv.cols[0].i64 = entries_fit ? C.dict_off : const_cast<int64_t*>(da.len);
+        tv.cols[0].chars = (uint8_t*)C.dict_chars;
+        int64_t bytes = 0;
+        if (C.dict_len == 0) {
+            if (hipMemsetAsync(C.dict_off, 0, 8, s) != hipSuccess) return LP_E_DEVICE;
+        } else {
+            if (hipMemcpyAsync(h->targs.p, &tv, sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess)
+                return LP_E_DEVICE;
+            if (lp::launch_table_values(d_args, d_targs, tv, h->d_buf, scratch, L.table_bytes, s) != 0) return LP_E_DEVICE;
+            if (hipMemcpyAsync(&bytes, tv.cols[0].i64 + C.dict_len, 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return LP_E_DEVICE;
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        C.dict_chars_len = (uint64_t)bytes;
+        if (!entries_fit || C.dict_chars_len > C.dict_chars_cap || (bytes && !C.dict_chars)) {
+            rc = LP_E_NOMEM;  // (the other columns' lengths are still set)
+            continue;
+        }
+        if (C.dict_len > 0 && lp::launch_table_chars(d_args, d_targs, tv, h->d_buf, s) != 0) return LP_E_DEVICE;
+        hipEventRecord(h->dev_ev[4], s);
+        if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+        for (int k = 0; k < 4; ++k) {
+            float t = 0;
+            hipEventElapsedTime(&t, h->dev_ev[k], h->dev_ev[k + 1]);
+            ms[k] += t;
+        }
+    }
+    if (rc == LP_OK)
+        for (int k = 0; k < 4; ++k) h->dms[k] = ms[k];
+    return rc;
+}
+
+// rows null: row k = line first + k
+static int table_dict_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                          lp_table_dict_col* cols, int n_cols, int threads) {
+    if (!h || !r || !cols || n_cols <= 0 || count > 0x7FFFFFFF) return LP_E_INVALID;
+    for (int c = 0; c < n_cols; ++c) {
+        const lp_table_dict_col& C = cols[c];
+        if (!C.path || !C.dict_off || C.dict_cap < 0 || (count > 0 && (!C.valid || !C.index))) return LP_E_INVALID;
+    }
+    // the plain STRING column of the path: its checks are this call's
+    std::vector<lp_table_col> tc((size_t)n_cols);
+    int64_t dummy_off[2] = {0, 0};
+    uint8_t dummy_valid = 0;
+    for (int c = 0; c < n_cols; ++c) {
+        tc[c] = lp_table_col{};
+        tc[c].path = cols[c].path;
+        tc[c].kind = LP_CAST_STRING;
+        tc[c].valid = cols[c].valid ? cols[c].valid : &dummy_valid;
+        tc[c].i64 = dummy_off;
+    }
+    if (!r->on_host) {
+        // table_any's checks of a STRING column's path, and of the view
+        for (int c = 0; c < n_cols; ++c) {
+            std::string p = cols[c].path;
+            if (const int pk = lp::Plan::pseudo_kind(p)) {
+                if (pk != lp::TC_LINE) return LP_E_INVALID;
+                continue;
+            }
+            int casts = h->plan.casts(p);
+            if (casts < 0) {
+                const size_t dot = p.rfind('.');
+                if (dot != std::string::npos) casts = h->plan.casts(p.substr(0, dot) + ".*");
+            }
+            if (casts < 0) return LP_E_MISSING;
+            if (!(casts & LP_CAST_STRING)) return LP_E_INVALID;
+        }
+        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
+            r->line_off != h->line_off.as<uint64_t>())
+            return LP_E_STATE;
+        return table_dict_device(h, first, count, rows, cols, n_cols);
+    }
+    // a host copy: the host table's plain column, then a hash map in row order
+    std::vector<std::vector<int64_t>> off((size_t)n_cols, std::vector<int64_t>((size_t)count + 1, 0));
+    std::vector<std::vector<char>> chars((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) tc[c].i64 = off[c].data();
+    int st = table_any(h, r, first, count, rows, tc.data(), n_cols, threads);
+    if (st == LP_E_NOMEM) {
+        for (int c = 0; c < n_cols; ++c) {
+            chars[c].resize((size_t)tc[c].chars_len + 1);
+            tc[c].chars = chars[c].data();
+            tc[c].chars_cap = tc[c].chars_len;
+        }
+        st = table_any(h, r, first, count, rows, tc.data(), n_cols, threads);
+    }
+    if (st != LP_OK) return st;
+    int rc = LP_OK;
+    for (int c = 0; c < n_cols; ++c) {
+        lp_table_dict_col& C = cols[c];
+        const int64_t* o = off[c].data();
+        const char* b = chars[c].data();
+        std::unordered_map<std::string_view, int32_t> seen;
+        std::vector<int64_t> first_row;  // per entry: its first row
+        std::vector<int32_t> idx((size_t)count, 0);
+        uint64_t bytes = 0;
+        for (int64_t k = 0; k < count; ++k) {
+            if (!C.valid[k]) continue;
+            const std::string_view v(b ? b + o[k] : "", (size_t)(o[k + 1] - o[k]));
+            auto it = seen.find(v);
+            if (it == seen.end()) {
+                it = seen.emplace(v, (int32_t)first_row.size()).first;
+                first_row.push_back(k);
+                bytes += v.size();
+            }
+            idx[(size_t)k] = it->second;
+        }
+        C.dict_len = (int64_t)first_row.size();
+        C.dict_chars_len = bytes;
+        if (C.dict_len > C.dict_cap || bytes > C.dict_chars_cap || (bytes && !C.dict_chars)) {
+            rc = LP_E_NOMEM;
+            continue;
+        }
+        if (count > 0) memcpy(C.index, idx.data(), 4 * (size_t)count);
+        uint64_t pos = 0;
+        for (size_t j = 0; j < first_row.size(); ++j) {
+            const int64_t k = first_row[j];
+            C.dict_off[j] = (int64_t)pos;
+            if (o[k + 1] > o[k]) memcpy(C.dict_chars + pos, b + o[k], (size_t)(o[k + 1] - o[k]));
+            pos += (uint64_t)(o[k + 1] - o[k]);
+        }
+        C.dict_off[first_row.size()] = (int64_t)pos;
+    }
+    return rc;
+}
+
+int lp_result_table_dict(lp_handle* h, const lp_result* r, int64_t first, int64_t count, lp_table_dict_col* cols,
+                         int n_cols, int threads) {
+    return table_dict_any(h, r, first, count, nullptr, cols, n_cols, threads);
+}
+
+int lp_result_table_dict_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows,
+                              lp_table_dict_col* cols, int n_cols, int threads) {
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
+    return table_dict_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
 }
 
 // ---- wildcard targets as map columns (ParsedRecord.setMultiValueString)

@@ -112,9 +112,10 @@ size_t table_srcw_offset(int64_t count);
 // lp_table.h): ta.bad_row is then zeroed by launch_table_values and read by the
 // caller with the STRING totals
 bool table_ext(const TableArgs& ta);
-// mid (optional): recorded after k_table_values, before the offset scans
+// mid (optional): recorded after k_table_values, before the offset scans;
+// offsets false: no scans, a STRING column's i64[k + 1] stays row k's length
 int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
-                        void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid = nullptr);
+                        void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid = nullptr, bool offsets = true);
 int launch_table_chars(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
                        hipStream_t s);
 
@@ -138,6 +139,32 @@ int launch_map_count(const DeviceArgs* d_args, MapArgs& ma, void* scratch, size_
 int launch_map_entries(const DeviceArgs* d_args, MapArgs& ma, const uint8_t* buf, void* scratch, size_t scratch_bytes,
                        hipStream_t s, const void* totals[3]);
 int launch_map_fill(MapArgs& ma, int64_t n_entries, void* scratch, size_t scratch_bytes, hipStream_t s);
+
+// a dictionary-encoded STRING column of the device table (dict.hip, lp_table.h
+// DictArgs, lp_dict.h), one column at a time in one scratch.  DictLayout: the
+// byte offsets of the column's scratch arrays for count rows.  `table` is the
+// scratch launch_table_values gets for the dictionary's values; the slot
+// table, dead by then, shares its bytes; `dump` (the validity bytes of the
+// dictionary's rows, all 1) shares the slot words'.  Per row: 8 + 8 (table /
+// slots, 2 count + 1 words) + 8 (len) + 8 (srcw) + 4 (slot) + 4 + 4 (flag, rank)
+// + 8 (reps) = 44 bytes, plus the scans' temporaries.
+//   launch_dict_insert  the table reset (every call), then one lane per valid
+//                       row: hash, probe, claim or min
+//   launch_dict_rank    the representatives' flags and their scan; *total: the
+//                       device word that will hold the dictionary's length
+//   launch_dict_index   index[k], and the representatives' lines (rows null:
+//                       first + k) for the dictionary's values
+struct DictLayout {
+    size_t table, table_bytes, len, srcw, slot, flag, rank, reps, tmp, tmp_bytes, words, total;
+    uint32_t cap;
+};
+DictLayout dict_layout(int64_t count);
+// binds da's scratch pointers and ta's (one STRING column: i64 = len, srcw, bad_row)
+void dict_bind(DictArgs& da, TableArgs& ta, const DictLayout& L, void* scratch);
+int launch_dict_insert(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const DictArgs& da,
+                       const uint8_t* buf, hipStream_t s);
+int launch_dict_rank(const DictArgs& da, const DictLayout& L, void* scratch, hipStream_t s, const uint32_t** total);
+int launch_dict_index(const TableArgs& ta, const DictArgs& da, hipStream_t s);
 
 // lp_result_select on a device view (select.hip): the lines of [first, first +
 // count) (count > 0) whose status is in mask, ascending, as int64 line indices.

@@ -119,4 +119,27 @@ struct MapArgs {
     LP_G uint64_t *ksrc, *vsrc, *ksrc_e, *vsrc_e;
 };
 
+// ---- a dictionary-encoded STRING column (lp_result_table_dict on a device
+// view, dict.hip).  Kernel arguments passed by value; the column itself is
+// cols[0] of a one-column TableArgs, whose k_table_values run left each row's
+// validity (valid), length (len[k + 1]) and source word (srcw[k]).  Scratch:
+// slots [cap] the open-addressing table of row numbers (lp_dict.h), slot [count]
+// the slot each valid row ended in, flag / rank [count] the representatives
+// (a row whose slot holds the row itself) and their inclusive scan
+// (rank[count - 1] = the dictionary's length), reps [count] the representatives'
+// lines in ascending row order: the row list the dictionary's values are
+// built from.
+struct DictArgs {
+    int64_t count;
+    uint32_t cap;
+    int32_t hash_bits;  // LP_OPT_DICT_HASH_BITS
+    const LP_G uint8_t* valid;
+    const LP_G int64_t* len;
+    const LP_G uint64_t* srcw;
+    LP_G uint32_t *slots, *slot, *flag, *rank;
+    LP_G uint32_t* fail;  // set when a probe ran out
+    LP_G int32_t* index;  // the caller's [count]
+    LP_G int64_t* reps;
+};
+
 }  // namespace lp

@@ -30,381 +30,13 @@
 
 #include "kernels.h"
 #include "lp_device.h"
+#include "table_value.h"  // TVal, tvalue, row_view, row_line
 
 namespace lp {
 
 namespace {
 
 constexpr int TB = 256;
-
-// one value: 0 none (null / not delivered), 1 bytes at p (amp: a '&' first),
-// 2 a long, 3 bytes in buf
-struct TVal {
-    int kind = 0;
-    const LP_G uint8_t* p = nullptr;
-    uint32_t n = 0;
-    bool amp = false;
-    int64_t l = 0;
-    char buf[20];  // formatted values (dates, times, month names, binary IPs)
-};
-
-__constant__ char MONTH_TEXT[] = "JanuaryFebruaryMarchAprilMayJuneJulyAugustSeptemberOctoberNovemberDecember";
-__constant__ uint8_t MONTH_OFF[13] = {0, 7, 15, 20, 25, 28, 32, 36, 42, 51, 58, 66, 74};
-
-__device__ __forceinline__ void put2(char* b, int64_t v) {
-    b[0] = (char)('0' + v / 10);
-    b[1] = (char)('0' + v % 10);
-}
-
-__device__ __forceinline__ uint32_t digits(int64_t l) {
-    uint64_t u = l < 0 ? 0 - (uint64_t)l : (uint64_t)l;
-    uint32_t n = 1;
-    while (u >= 10) { u /= 10; ++n; }
-    return n + (l < 0 ? 1u : 0u);
-}
-
-__device__ __forceinline__ void write_long(LP_G uint8_t* d, int64_t l, uint32_t n) {  // n = digits(l)
-    uint64_t u = l < 0 ? 0 - (uint64_t)l : (uint64_t)l;
-    uint32_t k = n;
-    do {
-        d[--k] = (uint8_t)('0' + u % 10);
-        u /= 10;
-    } while (u);
-    if (l < 0) d[0] = '-';
-}
-
-// Long.parseLong (the host table's java_parse_long)
-__device__ bool parse_long(const LP_G uint8_t* p, uint32_t n, bool amp, int64_t& out) {
-    if (amp || n == 0) return false;
-    uint32_t k = 0;
-    bool neg = false;
-    if (p[0] == '-' || p[0] == '+') { neg = p[0] == '-'; k = 1; }
-    if (k == n) return false;
-    uint64_t v = 0;
-    for (; k < n; ++k) {
-        const uint32_t d = p[k] - '0';
-        if (d > 9) return false;
-        if (v > (0x8000000000000000ull - d) / 10) return false;  // past 2^63
-        v = v * 10 + d;
-    }
-    if (!neg && v == 0x8000000000000000ull) return false;
-    out = neg ? (int64_t)(0 - v) : (int64_t)v;
-    return true;
-}
-
-// Double.parseDouble of "I.F" (digits '.' digits, each at most 18 digits:
-// a SECOND_MILLIS upstream list item, UpstreamModule's element kind):
-// correctly rounded, as Java's parse (IEEE round half to even).  S = I *
-// 10^f + F and the value is S / 10^f: exact by one IEEE division when S <
-// 2^53 and f <= 22 (both operands exact); else the quotient's 54-55
-// leading bits by binary long division in 128-bit integers (S < 2^120),
-// rounded with the remainder as the sticky bit.
-__device__ double decimal_to_double(const LP_G uint8_t* p, uint32_t n) {
-    typedef unsigned __int128 u128;
-    uint64_t I = 0, F = 0;
-    uint32_t q = 0;
-    int f = 0;
-    for (; q < n && p[q] != '.'; ++q) I = I * 10u + (p[q] - '0');
-    for (++q; q < n; ++q, ++f) F = F * 10u + (p[q] - '0');
-    u128 D = 1;
-    for (int k = 0; k < f; ++k) D *= 10u;
-    const u128 S = (u128)I * D + F;
-    if (S == 0) return 0.0;
-    if (S < ((u128)1 << 53) && f <= 22) return (double)(uint64_t)S / (double)(uint64_t)D;
-    auto bitlen = [](u128 x) {
-        const uint64_t hi = (uint64_t)(x >> 64), lo = (uint64_t)x;
-        return hi ? 128 - __builtin_clzll(hi) : lo ? 64 - __builtin_clzll(lo) : 0;
-    };
-    const int k = 54 - (bitlen(S) - bitlen(D));  // S * 2^k / D in [2^53, 2^55)
-    u128 N = S, Dn = D;
-    if (k >= 0) N <<= k;
-    else Dn <<= -k;
-    uint64_t quo = 0;
-    for (int b = 55; b >= 0; --b) {
-        const u128 t = Dn << b;
-        if (N >= t) {
-            N -= t;
-            quo |= 1ull << b;
-        }
-    }
-    const int shift = quo >= (1ull << 54) ? 2 : 1;  // keep 53 significant bits
-    const uint64_t half = 1ull << (shift - 1), r = quo & ((1ull << shift) - 1);
-    uint64_t m = quo >> shift;
-    if (r > half || (r == half && (N != 0 || (m & 1u)))) ++m;
-    return ldexp((double)m, shift - k);
-}
-
-// ResponseSetCookieDissector.dissect (dissectors/ResponseSetCookieDissector.java:86-135) on one
-// cookie string [cp, cp + cn) -- the cookie's LAST cookie string (every
-// dissection of a name reads the Parsable's cached last value,
-// core/Parsable.java:172-183): split(";"), each part trimmed and split("=", 2),
-// key and value trimmed; part 0's value is "value", a later part keyed
-// "expires" / "domain" / "comment" / "path" delivers that output (the last such
-// part wins, ParsedRecord).  Out of line: the table kernels' other columns
-// keep their registers.  kind / p / n / l as TVal.
-__device__ __noinline__ void setcookie_attr(const LP_G uint8_t* cp, uint32_t cn, int fld, int& kind,
-                                            const LP_G uint8_t*& p, uint32_t& n, int64_t& l) {
-    auto pk = [](const char* k) {
-        uint64_t x = 0;
-        for (int q = 0; k[q]; ++q) x |= (uint64_t)(uint8_t)k[q] << (8 * q);
-        return x;
-    };
-    const uint64_t want = fld == SC_DOMAIN ? pk("domain") : fld == SC_COMMENT ? pk("comment") : fld == SC_PATH ? pk("path")
-                                                                                                    : pk("expires");
-    const uint32_t klen = fld == SC_DOMAIN ? 6u : fld == SC_COMMENT ? 7u : fld == SC_PATH ? 4u : 7u;
-    for (uint32_t ps = 0, part = 0; ps <= cn; ++part) {
-        uint32_t pe = ps;
-        while (pe < cn && cp[pe] != ';') ++pe;
-        uint32_t a = ps, b = pe;
-        while (a < b && cp[a] <= ' ') ++a;
-        while (b > a && cp[b - 1] <= ' ') --b;
-        uint32_t x = a;
-        while (x < b && cp[x] != '=') ++x;
-        uint32_t ka = a, kb = x, va = x < b ? x + 1 : b, vb = b;
-        while (kb > ka && cp[kb - 1] <= ' ') --kb;
-        while (va < vb && cp[va] <= ' ') ++va;
-        if (part == 0) {
-            if (fld == SC_VALUE) { kind = 1; p = cp + va; n = vb - va; }
-        } else if (fld != SC_VALUE && kb - ka == klen) {
-            uint64_t k = 0;
-            for (uint32_t q = 0; q < klen; ++q) k |= (uint64_t)cp[ka + q] << (8 * q);
-            if (k == want) {
-                if (fld == SC_EXPIRES_S || fld == SC_EXPIRES_MS) {
-                    // parseExpire: "EEE, dd-MMM-yyyy HH:mm:ss GMT" (the only layout the
-                    // phase-1 guard lets through) -> epoch seconds * 1000; STRING:expires
-                    // is that / 1000 (ResponseSetCookieDissector.java:104-107, 137-150)
-                    const LP_G uint8_t* d = cp + va;
-                    int mon = 1;
-                    for (int q = 0; q < 12; ++q)
-                        if (d[8] == (uint8_t)MONTH_TEXT[MONTH_OFF[q]] && d[9] == (uint8_t)MONTH_TEXT[MONTH_OFF[q] + 1] &&
-                            d[10] == (uint8_t)MONTH_TEXT[MONTH_OFF[q] + 2])
-                            mon = q + 1;
-                    auto d2 = [&](int q) { return (int)(d[q] - '0') * 10 + (int)(d[q + 1] - '0'); };
-                    const int64_t days = days_from_civil(d2(12) * 100 + d2(14), mon, d2(5));
-                    const int64_t ms = (days * 86400 + d2(17) * 3600 + d2(20) * 60 + d2(23)) * 1000;
-                    kind = 2;
-                    l = fld == SC_EXPIRES_S ? ms / 1000 : ms;
-                } else {
-                    kind = 1;
-                    p = cp + va;
-                    n = vb - va;
-                }
-            }
-        }
-        ps = pe + 1;
-    }
-}
-
-__device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, const TableSrc& s, int64_t i,
-                       const LP_G uint8_t* line, const LP_G uint8_t* region) {
-    TVal v;
-    auto bytes = [&](const LP_G uint8_t* p, uint32_t n) {
-        v.kind = 1;
-        v.p = p;
-        v.n = n;
-    };
-    auto span = [&](uint32_t sp) { bytes(line + (sp & 0xFFFFu), (sp >> 16) - (sp & 0xFFFFu)); };
-    auto ref = [&](uint64_t r) {
-        bytes((ref_arena(r) ? region : line) + ref_off(r), ref_len(r));
-        v.amp = ref_amp(r);
-    };
-    auto along = [&](int64_t l) {
-        v.kind = 2;
-        v.l = l;
-    };
-    switch (s.kind) {
-    case TC_TOKEN: case TC_CLF2NUM: case TC_NUM2CLF: {
-        const bool null = (C.tok_flags[i] >> s.a) & 1u;
-        if (null) {
-            if (s.kind == TC_CLF2NUM) along(0);  // ConvertCLFIntoNumber: null -> 0L
-            return v;
-        }
-        span(C.tok_span[s.a][i]);
-        if (s.kind == TC_NUM2CLF && v.n == 1 && v.p[0] == '0') v.kind = 0;  // "0" -> null
-        return v;
-    }
-    case TC_TIME: {
-        const TimeStage& TS = P.time[s.a];
-        const uint32_t sp = C.tok_span[TS.tok][i];
-        if (((C.tok_flags[i] >> TS.tok) & 1u) || (sp >> 16) <= (sp & 0xFFFFu)) return v;  // null / empty: no dissection
-        if (s.b == TF_EPOCH) { along(C.t_epoch[s.a][i]); return v; }
-        const uint64_t w = s.c ? C.t_utc[s.a][i] : C.t_local[s.a][i];
-        const int64_t Y = w & 0xFFFF, MO = (w >> 16) & 15, D = (w >> 20) & 31, H = (w >> 25) & 31, MI = (w >> 30) & 63,
-                      S = (w >> 36) & 63, WY = (w >> 42) & 0xFFFF, WK = (w >> 58) & 63;
-        const int64_t nanos = TS.kind == TK_STRF ? (int64_t)C.t_nano[s.a][i] : 0;
-        switch (s.b) {
-        case TF_DAY: along(D); break;
-        case TF_MONTH: along(MO); break;
-        case TF_WEEK: along(WK); break;
-        case TF_WEEKYEAR: along(WY); break;
-        case TF_YEAR: along(Y); break;
-        case TF_HOUR: along(H); break;
-        case TF_MINUTE: along(MI); break;
-        case TF_SECOND: along(S); break;
-        case TF_MILLI: along(nanos / 1000000); break;
-        case TF_MICRO: along(nanos / 1000); break;
-        case TF_NANO: along(nanos); break;
-        case TF_MONTHNAME:
-            v.kind = 3;
-            v.n = MONTH_OFF[MO] - MONTH_OFF[MO - 1];
-            for (uint32_t k = 0; k < v.n; ++k) v.buf[k] = MONTH_TEXT[MONTH_OFF[MO - 1] + k];
-            break;
-        case TF_DATE:  // "%04d-%02d-%02d"
-            v.kind = 3;
-            v.n = 10;
-            put2(v.buf, Y / 100);
-            put2(v.buf + 2, Y % 100);
-            v.buf[4] = '-';
-            put2(v.buf + 5, MO);
-            v.buf[7] = '-';
-            put2(v.buf + 8, D);
-            break;
-        case TF_TIME:  // "%02d:%02d:%02d"
-            v.kind = 3;
-            v.n = 8;
-            put2(v.buf, H);
-            v.buf[2] = ':';
-            put2(v.buf + 3, MI);
-            v.buf[5] = ':';
-            put2(v.buf + 6, S);
-            break;
-        default: break;
-        }
-        return v;
-    }
-    case TC_FL: {
-        const uint32_t kind = C.fl_kind[s.a][i];
-        if (kind == FL_NONE) return v;
-        if (s.b == 0) span(C.fl_method[s.a][i]);
-        else if (s.b == 1) span(C.fl_uri[s.a][i]);
-        else if (kind == FL_FULL) span(C.fl_proto[s.a][i]);  // a chopped line's protocol is null
-        return v;
-    }
-    case TC_PROTO: {  // HttpFirstLineProtocolDissector: "HTTP/x.y".split("/", 2)
-        if (C.fl_kind[s.a][i] != FL_FULL) return v;
-        span(C.fl_proto[s.a][i]);
-        if (v.n == 0 || (v.n == 1 && v.p[0] == '-')) { v.kind = 0; return v; }
-        uint32_t sl = 0;
-        while (sl < v.n && v.p[sl] != '/') ++sl;
-        if (sl == v.n) { v.kind = 0; return v; }  // no '/': both null
-        if (s.b == 0) v.n = sl;
-        else { v.p += sl + 1; v.n -= sl + 1; }
-        return v;
-    }
-    case TC_URI: {
-        const uint32_t f = C.u_flags[s.a][i];
-        if (!(f & UF_DONE)) return v;
-        switch (s.b) {
-        case UP_QUERY: ref(C.u_query[s.a][i]); break;
-        case UP_PATH: ref(C.u_path[s.a][i]); break;
-        case UP_REF: if (f & UF_FRAG) ref(C.u_frag[s.a][i]); break;
-        case UP_PROTOCOL: if ((f & UF_IS_URL) && (f & UF_SCHEME)) ref(C.u_scheme[s.a][i]); break;
-        case UP_HOST: if ((f & UF_IS_URL) && (f & UF_HOST)) ref(C.u_host[s.a][i]); break;
-        case UP_PORT: if ((f & UF_IS_URL) && (f & UF_PORT)) along(C.u_port[s.a][i]); break;
-        default: break;
-        }
-        return v;
-    }
-    case TC_SECMS:  // ConvertSecondsWithMillisStringDissector (+ ConvertMillisecondsIntoMicroseconds)
-        if (!((C.tok_flags[i] >> P.secms[s.a].tok) & 1u)) along(s.b ? (int64_t)((uint64_t)C.sm_ms[s.a][i] * 1000u) : C.sm_ms[s.a][i]);
-        return v;
-    case TC_BINIP: {  // BinaryIPDissector: "%d.%d.%d.%d" of the signed bytes
-        const uint32_t sp = C.tok_span[P.binip[s.a].tok][i];
-        if ((sp >> 16) - (sp & 0xFFFFu) != 16u) return v;
-        const uint32_t x = C.bip[s.a][i];
-        v.kind = 3;
-        v.n = 0;
-        for (int k = 0; k < 4; ++k) {
-            int b = (int)(int8_t)((x >> (8 * k)) & 0xFF);
-            if (k) v.buf[v.n++] = '.';
-            if (b < 0) { v.buf[v.n++] = '-'; b = -b; }
-            if (b >= 100) v.buf[v.n++] = (char)('0' + b / 100);
-            if (b >= 10) v.buf[v.n++] = (char)('0' + (b / 10) % 10);
-            v.buf[v.n++] = (char)('0' + b % 10);
-        }
-        return v;
-    }
-    case TC_LIST: case TC_LIST_MS: {  // UpstreamListDissector item b (its table in the line's region)
-        if ((uint32_t)s.b >= C.l_count[s.a][i]) return v;
-        const uint32_t ent = P.list[s.a].secms ? LIST_ENT_MS : LIST_ENT;
-        const LP_G uint8_t* e = region + ref_off(C.l_tab[s.a][i]) + (uint32_t)s.b * ent;
-        if (s.kind == TC_LIST) {
-            span(reinterpret_cast<const LP_G uint32_t*>(e)[s.c & 1]);
-        } else {
-            const int64_t ms = reinterpret_cast<const LP_G int64_t*>(e + 8)[s.c & 1];
-            along((s.c & 2) ? (int64_t)((uint64_t)ms * 1000u) : ms);
-        }
-        return v;
-    }
-    case TC_PAIR: {  // the cookie / parameter's last occurrence in the pair stage's piece table
-        const uint32_t cnt = C.p_count[s.a][i];
-        const LP_G uint64_t* t = reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.p_tab[s.a][i]));
-        for (uint32_t k = 0; k < cnt; ++k) {
-            const uint64_t nref = t[2 * k];
-            if (ref_len(nref) != (uint32_t)s.c) continue;
-            const LP_G uint8_t* np = (ref_arena(nref) ? region : line) + ref_off(nref);
-            bool same = true;
-            for (int q = 0; q < s.c && same; ++q) same = np[q] == T.names[s.b + q];
-            if (same) ref(t[2 * k + 1]);
-        }
-        return v;
-    }
-    case TC_SETC: {
-        const int j = s.a & 0xFF;
-        const uint32_t cnt = C.p_count[j][i];
-        const LP_G uint64_t* t = reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.p_tab[j][i]));
-        uint64_t cref = 0;
-        bool found = false;
-        for (uint32_t k = 0; k < cnt; ++k) {
-            const uint64_t nref = t[2 * k];
-            if (ref_len(nref) != (uint32_t)s.c) continue;
-            const LP_G uint8_t* np = (ref_arena(nref) ? region : line) + ref_off(nref);
-            bool same = true;
-            for (int q = 0; q < s.c && same; ++q) same = np[q] == T.names[s.b + q];
-            if (same) { cref = t[2 * k + 1]; found = true; }
-        }
-        if (found) setcookie_attr((ref_arena(cref) ? region : line) + ref_off(cref), ref_len(cref), s.a >> 8, v.kind, v.p, v.n, v.l);
-        return v;
-    }
-    case TC_QP: {  // the parameter's last occurrence (ParsedRecord: the last value wins)
-        const uint32_t cnt = C.q_count[s.a][i];
-        if (cnt == 0) return v;
-        const LP_G uint64_t* t = reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.q_params[s.a][i]));
-        for (uint32_t k = 0; k < cnt; ++k) {
-            const uint64_t nref = t[2 * k];
-            if (nref == REF_SKIP || ref_len(nref) != (uint32_t)s.c) continue;
-            const LP_G uint8_t* np = (ref_arena(nref) ? region : line) + ref_off(nref);
-            bool same = true;
-            for (int q = 0; q < s.c && same; ++q) same = np[q] == T.names[s.b + q];
-            if (same) ref(t[2 * k + 1]);
-        }
-        return v;
-    }
-    default:  // TC_NONE, TC_NULL
-        return v;
-    }
-}
-
-// the row's line and arena region (a program without URI stages writes no
-// region: nothing refers to one)
-__device__ __forceinline__ bool row_view(const Program& P, const Columns& C, const uint8_t* buf, int64_t i,
-                                         const LP_G uint8_t*& line, const LP_G uint8_t*& region) {
-    if (C.status[i] != ST_OK) return false;
-    line = (const LP_G uint8_t*)buf + C.line_off[i];
-    region = P.has_phase2() ? C.arena + C.arena_base[i] : C.arena;
-    return true;
-}
-
-// Row k's line of a row-list instance: rows[k] (null: first + k); false when
-// it is outside the batch (never dereferenced: *bad_row is set, every lane
-// that finds one stores the same 1)
-__device__ __forceinline__ bool row_line(const LP_G int64_t* rows, int64_t first, int64_t n_lines, LP_G uint32_t* bad_row,
-                                         int64_t k, int64_t& i) {
-    i = rows ? rows[k] : first + k;
-    if ((uint64_t)i < (uint64_t)n_lines) return true;
-    *bad_row = 1u;
-    return false;
-}
 
 template <bool EXT>
 __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restrict__ args,
@@ -844,7 +476,7 @@ bool table_ext(const TableArgs& ta) {
 }
 
 int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
-                        void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid) {
+                        void* scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t mid, bool offsets) {
     if (ta.count > 0x7FFFFFFF) return -1;  // the scan's item count is an int
     const int64_t n = ta.count;
     if (n == 0) {
@@ -859,6 +491,7 @@ int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, cons
         hipLaunchKernelGGL(k_table_values<false>, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
     }
     if (mid) hipEventRecord(mid, s);  // the values kernel done: the scans follow
+    if (!offsets) return hipGetLastError() == hipSuccess ? 0 : -1;  // i64[k + 1] stays row k's length (dict.hip)
     size_t tmp = 0;
     hipcub::DeviceScan::InclusiveSum(nullptr, tmp, (const int64_t*)nullptr, (int64_t*)nullptr, (int)n);
     const size_t tmp_al = (tmp + 255) & ~(size_t)255;
