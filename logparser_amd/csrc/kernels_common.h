@@ -14,6 +14,7 @@
 
 #include "kernels.h"
 #include "lp_device.h"
+#include "lp_owner.h"
 
 namespace lp {
 namespace {
@@ -233,20 +234,7 @@ __device__ __forceinline__ void load_elems(const Program& P, Elem* s_elems) {
     for (int k = lane_id(); k < P.n_elems; k += PW) s_elems[k] = P.elems[k];
 }
 
-// k-th set bit (0-based) of m (k < popcount(m))
-__device__ __forceinline__ uint32_t select64(uint64_t m, uint32_t k) {
-    uint32_t pos = 0, v = (uint32_t)m, c = (uint32_t)__popc(v);
-    if (k >= c) { k -= c; v = (uint32_t)(m >> 32); pos = 32; }
-    c = (uint32_t)__popc(v & 0xFFFFu);
-    if (k >= c) { k -= c; v >>= 16; pos += 16; }
-    c = (uint32_t)__popc(v & 0xFFu);
-    if (k >= c) { k -= c; v >>= 8; pos += 8; }
-    c = (uint32_t)__popc(v & 0xFu);
-    if (k >= c) { k -= c; v >>= 4; pos += 4; }
-    c = (uint32_t)__popc(v & 3u);
-    if (k >= c) { k -= c; v >>= 2; pos += 2; }
-    return pos + (k >= (v & 1u) ? 1u : 0u);
-}
+// (select64, the k-th set bit of a mask: lp_owner.h)
 __device__ __forceinline__ int lsb64(uint64_t m) { return (int)__builtin_ctzll(m); }
 __device__ __forceinline__ int msb64(uint64_t m) { return 63 - (int)__builtin_clzll(m); }
 
@@ -259,6 +247,25 @@ __device__ __forceinline__ T wave_incl_scan(T x) {
         if (lane >= d) x += y;
     }
     return x;
+}
+// The same scan of 32-bit values on the VALU's data-parallel primitives
+// (DPP) instead of six chained LDS-pipeline permutes: a shift by 1, 2, 4, 8
+// within each row of 16 lanes (a lane without a source keeps the 0 passed as
+// the old value), then lane 15 of a row added to the next row (rows 1 and
+// 3), then lane 31 to rows 2 and 3.  Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t x) {
+    constexpr int ROW_SHR = 0x110, ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143;
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_SHR + 1, 0xF, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_SHR + 2, 0xF, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_SHR + 4, 0xF, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_SHR + 8, 0xF, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_BCAST15, 0xA, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ROW_BCAST31, 0xC, 0xF, false);
+    return x;
+}
+// the value of lane l, l wave-uniform (v_readlane: no LDS-pipeline trip)
+__device__ __forceinline__ uint32_t lane_value(uint32_t x, int l) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, l);
 }
 template <typename T>
 __device__ __forceinline__ T wave_sum(T x) {

@@ -31,6 +31,60 @@ constexpr uint32_t URI_CAP = 8512;
 #define LP_URI_GR 9
 #endif
 
+// Which lane's line owns item g0 + lane of a cooperative pass (the gather's
+// blocks, the walk's events, the piece pass's pieces; lp_owner.h): the
+// lanes' items numbered line after line, `first` = the exclusive prefix sum
+// of the counts.  The kernel is bound by VALU issue more than by latency, so
+// the lookup is kept to a few VALU instructions and two LDS reads: the
+// owner's rank among the non-empty lanes from the round's head mask
+// (owner_rank), then the rank table, which holds select64(N, r) and that
+// lane's first item for every r (each non-empty lane writes its own entry,
+// once per pass).  The head masks of OWNER_WORDS rounds at a time live in
+// LDS: fill(b0) has every non-empty lane whose first item lies in
+// [b0, b0 + 64 OWNER_WORDS) OR its bit into its round's word (workgroups are
+// one wave: the barriers only order the LDS accesses).  All wave-uniform
+// control flow; every lane takes part.
+constexpr int OWNER_WORDS = LP_URI_GR;
+constexpr int OWNER_LDS_WORDS = OWNER_WORDS + PW / 2;  // uint64_t: the head words, then PW 32-bit table entries
+struct OwnerRounds {
+    uint64_t* hw;
+    uint32_t* tab;   // entry r: the r-th non-empty lane | its first item << 6
+    uint32_t first;  // this lane's first item
+    bool has;        // this lane has items
+    uint32_t b0;     // the first item of the filled rounds
+
+    __device__ __forceinline__ OwnerRounds(uint64_t* words, uint32_t first_item, uint32_t cnt)
+        : hw(words), tab(reinterpret_cast<uint32_t*>(words + OWNER_WORDS)), first(first_item), has(cnt != 0), b0(0) {
+        const uint64_t N = __ballot(has);
+        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(N >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)N, 0u));
+        __syncthreads();  // the previous pass has read its table
+        if (has) tab[r] = (uint32_t)lane_id() | first << 6;  // (r < 64; read after fill's barriers)
+    }
+    __device__ __forceinline__ void fill(uint32_t from) {  // from: a multiple of 64
+        b0 = from;
+        __syncthreads();  // the previous rounds' words are read
+        if (lane_id() < OWNER_WORDS) hw[lane_id()] = 0;
+        __syncthreads();
+        const uint32_t r = (first - from) >> 6;
+        if (has && first >= from && r < (uint32_t)OWNER_WORDS)
+            atomicOr(reinterpret_cast<unsigned long long*>(hw + r), 1ull << (first & 63u));
+        __syncthreads();
+    }
+    // fill before the rounds [g0, g0 + 64 OWNER_WORDS) of a pass that starts at item 0
+    __device__ __forceinline__ void fill_at(uint32_t g0) {
+        if ((g0 >> 6) % (uint32_t)OWNER_WORDS == 0) fill(g0);
+    }
+    // The owner lane of item g0 + lane (g0 a filled round's first item,
+    // wave-uniform, below the pass's total: the rank is then at least 1) and
+    // that lane's first item.
+    __device__ __forceinline__ int owner(uint32_t g0, uint32_t& ofirst) const {
+        const uint32_t K = (uint32_t)__popcll(__ballot(has && first < g0));
+        const uint32_t e = tab[owner_rank(K, hw[(g0 - b0) >> 6], lane_id()) - 1u];
+        ofirst = e >> 6;
+        return (int)(e & 63u);
+    }
+};
+
 // Per lane: the line's URI sources.  sp[u] = a | b << 16 (line-relative, 0 =
 // none), cs[u] = the compact buffer offset of line byte a.  NU: the URI
 // stages this kernel instance handles (>= P.n_uri; most programs have at
@@ -102,16 +156,13 @@ __device__ __forceinline__ UriLane<NU> uri_lane(const Program& P, const Columns&
 // LogFormat, -1 none): an event takes its owner line's table flag.
 template <bool SLOT, typename CL>
 __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL& L, bool part, int a, int b,
-                                              uint32_t usep, const Arena& A, UriWalk& Wk) {
+                                              uint32_t usep, const Arena& A, uint64_t* heads, UriWalk& Wk) {
     const int lane = lane_id();
     const bool table = u >= 0 && P.uri[u].want_query && P.uri[u].query_stage >= 0;  // uniform unless SLOT
     const uint32_t cnt = part ? usep : 0u;
-    uint32_t x = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    const uint32_t eb = x - cnt, E = __shfl(x, 63);
+    const uint32_t x = wave_incl_scan_dpp(cnt);
+    const uint32_t eb = x - cnt, E = lane_value(x, 63);
+    OwnerRounds OW(heads, eb, cnt);
     const uint32_t tab = (A.used + 15) & ~15u;
     const unsigned long long reg = (unsigned long long)(uintptr_t)A.p;
     // the owner's state (this lane's line)
@@ -121,10 +172,9 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
     for (uint32_t g0 = 0; g0 < E; g0 += PW) {
         const uint32_t g = g0 + (uint32_t)lane;
         const bool valid = g < E;
-        int ow = 0;  // last lane whose first event is <= g
-        for (int st = 32; st; st >>= 1)
-            if (__shfl((int)eb, ow + st) <= (int)g) ow += st;
-        const uint32_t ebo = (uint32_t)__shfl((int)eb, ow);
+        OW.fill_at(g0);
+        uint32_t ebo;  // the owner's first event
+        const int ow = OW.owner(g0, ebo);  // last lane whose first event is <= g
         const uint32_t oo = (uint32_t)__shfl((int)L.o, ow);
         const int oa = __shfl(a, ow), ob = __shfl(b, ow);
         // the event: the (g - ebo)-th UEV bit of the owner's [oa, ob)
@@ -235,7 +285,8 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
 // caller to redo it (k_uri_overflow, which also works the list off).
 template <int NU, int NQ, bool COOP, bool SLOT, bool QUEUE, typename LU, typename LL>
 __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, UriLane<NU>& U, LU&& lu, LL&& ll,
-                                         bool active, int64_t li, int64_t wave, WaveCounts& WC, bool& redo) {
+                                         bool active, int64_t li, int64_t wave, uint64_t* heads, WaveCounts& WC,
+                                         bool& redo) {
     const int lane = lane_id();
     const int nq = P.n_query < NQ ? P.n_query : NQ;
     uint32_t need = 0;
@@ -261,12 +312,10 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
     if (lend) ll(lend, [&](const auto& LH) { need += list_need(P, U.fmt, LH, C, li) + pair_need(P, U.fmt, LH, C, li); });
     need = (need + 15) & ~15u;
     // wave-aggregated arena allocation from the wave's shard
-    uint32_t x = need;
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    const uint32_t total = __shfl(x, 63);
+    LP_PROF(29);
+    const uint32_t x = wave_incl_scan_dpp(need);
+    const uint32_t total = lane_value(x, 63);
+    LP_PROF(20);
     const int shard = (int)(wave % ARENA_SHARDS);
     unsigned long long wbase = 0;
     // regions start 16-byte aligned (their query tables take 16-byte slot
@@ -325,7 +374,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
         UriWalk Wk;
         if constexpr (COOP) {
             LP_PROF(50 + 4 * sl);
-            uri_walk_coop<SLOT>(P, u, lu(u), part, a, b, U.usep.get(u), A, Wk);
+            uri_walk_coop<SLOT>(P, u, lu(u), part, a, b, U.usep.get(u), A, heads, Wk);
             LP_PROF(51 + 4 * sl);
         } else if (part) {
             uri_walk_fast(P, u, lu(u), a, b, U.usep.get(u), A, Wk);
@@ -364,12 +413,9 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
         uint64_t piece_ovf = 0;  // lanes whose line lost a piece for want of arena
         uint32_t np = 0;
         for (int qs = 0; qs < nq; ++qs) np += has ? o.qpend.get(qs) : 0u;
-        uint32_t incl = np;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(incl, d);
-            if (lane >= d) incl += y;
-        }
-        const uint32_t base = incl - np, tot = __shfl(incl, 63);
+        const uint32_t incl = wave_incl_scan_dpp(np);
+        const uint32_t base = incl - np, tot = lane_value(incl, 63);
+        OwnerRounds OW(heads, base, np);
         // piece j of lane ow: its query stage and its slot in ow's region;
         // OL = ow's line view of that stage (every lane takes part in the shuffles)
         auto piece = [&](int ow, uint32_t j, int& pq, uint32_t& soff) {
@@ -406,11 +452,10 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
                 t0[k] = 0;
                 if (g0 + (uint32_t)(k * PW) >= tot) continue;  // no piece in this block (uniform)
                 const uint32_t g = g0 + (uint32_t)(k * PW + lane);
-                int ow = 0;  // last lane whose first pending piece index is <= g
-                for (int st = 32; st; st >>= 1)
-                    if (__shfl(base, ow + st) <= g) ow += st;
+                OW.fill_at(g0 + (uint32_t)(k * PW));
+                uint32_t ob;  // the owner's first pending piece index
+                const int ow = OW.owner(g0 + (uint32_t)(k * PW), ob);  // last lane whose first piece index is <= g
                 own[k] = ow;
-                const uint32_t ob = __shfl(base, ow);
                 const unsigned long long oab = __shfl(my_ab, ow);
                 piece(ow, g - ob, pqs[k], soffs[k]);
                 if (g < tot) t0[k] = *reinterpret_cast<const LP_G uint64_t*>(C.arena + oab + soffs[k]);
@@ -429,12 +474,8 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
             LP_PROF(18);
             // the round's spilled bytes in one allocation from the wave's
             // shard (every owner is a line of this wave)
-            uint32_t x = mine;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (lane >= d) x += y;
-            }
-            const uint32_t rtot = __shfl(x, 63);
+            const uint32_t x = wave_incl_scan_dpp(mine);
+            const uint32_t rtot = lane_value(x, 63);
             unsigned long long rbase = 0;
             if (lane == 63 && rtot) rbase = atomicAdd(&C.meta->shard_top[16 * shard], (unsigned long long)rtot);
             unsigned long long at = __shfl(rbase, 63) + x - mine;  // this lane's first piece in the shard
@@ -497,7 +538,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
 template <int NU, int NQ, bool SLOT, uint32_t CAP>
 __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uint64_t nbytes, const Program& P,
                                             const Columns& C, int64_t wave, int64_t n_lines, uint32_t* cbuf,
-                                            uint64_t* plane, WaveCounts& WC, bool& redo) {
+                                            uint64_t* plane, uint64_t* heads, WaveCounts& WC, bool& redo) {
     const int lane = lane_id();
     const int64_t li = wave * PW + lane;
     const bool active = li < n_lines;
@@ -537,22 +578,19 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
     const uint64_t q0 = l1 ? l0 & ~15ull : 0;
     const uint32_t nb2 = l1 ? (uint32_t)((((l1 + 15) & ~15ull) - q0) >> 4) : 0u;
     auto blocks = [&](uint32_t n, uint32_t& first) {  // the wave's block count, this line's first block
-        uint32_t x = n;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
+        const uint32_t x = wave_incl_scan_dpp(n);
         first = x - n;
-        return (uint32_t)__shfl(x, 63);
+        return lane_value(x, 63);
     };
-    uint32_t cb;
-    uint32_t tot = blocks(nb1 + nb2, cb);
+    uint32_t cb, nb = nb1 + nb2;  // this line's blocks
+    uint32_t tot = blocks(nb, cb);
     // the list / pair tokens in LDS when the wave's bytes fit with them, else
     // read from HBM (only the URI bytes decide whether the wave fits)
     bool lin = lists;
     if (lists && 16 * tot + 16 > CAP) {
         lin = false;
-        tot = blocks(nb1, cb);
+        nb = nb1;
+        tot = blocks(nb, cb);
     }
     if (16 * tot + 16 > CAP) return false;
     WC.gathered = 16 * tot;
@@ -561,26 +599,29 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
         if (s) U.cs.set(u, 16 * cb + (uint32_t)(U.ls + (s & 0xFFFF) - r0));
     }
     // gather: block g of the wave is block g - cb[own] of line own's region,
-    // own = the last lane whose first block is <= g; every round's load in
-    // flight before the first store
+    // own = the last lane whose first block is <= g (OwnerRounds: a batch's
+    // head masks filled at once); every round's load in flight before the
+    // first store
     constexpr int GR = LP_URI_GR;  // rounds per batch (the main kernel's CAP / 1024, rounded up)
     uint16_t* pl16 = reinterpret_cast<uint16_t*>(plane);
+    OwnerRounds OW(heads, cb, nb);
     for (uint32_t g0 = 0; g0 < tot; g0 += GR * PW) {
         u32x4 v[GR];
+        OW.fill(g0);
 #pragma unroll
         for (int k = 0; k < GR; ++k) {
+            v[k] = u32x4{0, 0, 0, 0};
+            if (g0 + (uint32_t)(k * PW) >= tot) continue;  // no block in this round (uniform)
             const uint32_t g = g0 + (uint32_t)(k * PW + lane);
-            int own = 0;
-            for (int st = 32; st; st >>= 1)
-                if (__shfl(cb, own + st) <= g) own += st;
-            const uint32_t j = g - (uint32_t)__shfl(cb, own);  // block j of line own's regions
+            uint32_t ocb;  // the owner's first block
+            const int own = OW.owner(g0 + (uint32_t)(k * PW), ocb);
+            const uint32_t j = g - ocb;  // block j of line own's regions
             uint64_t src = (uint64_t)__shfl((unsigned long long)r0, own) + 16ull * j;
             if (lin) {  // (every lane in the shuffles: a permute reads no value from an inactive lane)
                 const uint32_t n1 = (uint32_t)__shfl(nb1, own);
                 const uint64_t s1 = (uint64_t)__shfl((unsigned long long)q0, own);
                 if (j >= n1) src = s1 + 16ull * (j - n1);
             }
-            v[k] = u32x4{0, 0, 0, 0};
             if (g < tot) v[k] = load16(buf, nbytes, src);
         }
         LP_PROF(28);
@@ -617,7 +658,7 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
         if (lin) f(LineT<lds_bytes>{(lds_bytes)cbuf, lorig, lend});
         else f(LineT<const LP_G uint8_t*>{lsp - lmis, lmis, lend});
     };
-    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, WC, redo);
+    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, heads, WC, redo);
     return true;
 }
 
@@ -636,9 +677,10 @@ __global__ __launch_bounds__(PW, SLOT ? LP_URI_SLOT_WPE : 4) void k_uri_lines(co
     if (wave * PW >= n_lines || C.meta->cap_ovf) return;
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP / 4 + 16];
     __shared__ uint64_t plane[URI_CAP / 64 + 1];
+    __shared__ uint64_t heads[OWNER_LDS_WORDS];  // (with cbuf and plane within 10,240 B: 16 workgroups per CU)
     WaveCounts WC;
     bool redo;  // (unused: this kernel queues such lines)
-    if (uri_compact<NU, NQ, SLOT, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC, redo)) WC.store(C, wave);
+    if (uri_compact<NU, NQ, SLOT, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) WC.store(C, wave);
     else if (lane_id() == 0) C.uri_ovf_list[atomicAdd(&C.meta->uri_ovf_waves, 1ull)] = (uint32_t)wave;
 }
 
@@ -734,11 +776,12 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
     const uint64_t nfix = min((uint64_t)(uint32_t)C.meta->uri_fix_lines, (uint64_t)C.cap_lines);
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP_OVF / 4 + 16];
     __shared__ uint64_t plane[URI_CAP_OVF / 64 + 1];
+    __shared__ uint64_t heads[OWNER_LDS_WORDS];
     for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
         const int64_t wave = C.uri_ovf_list[q];
         WaveCounts WC;
         bool redo = false;
-        if (!uri_compact<NU, NQ, SLOT, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, WC, redo)) {
+        if (!uri_compact<NU, NQ, SLOT, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) {
             const WaveLines W = wave_lines(C, wave, n_lines, nbytes);
             UriLane<NU> U = uri_lane<NU>(P, C, W.li, W.active);
             const LP_G uint8_t* ls = (const LP_G uint8_t*)(buf) + W.s;
@@ -746,7 +789,7 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
             const LineT<const LP_G uint8_t*> L{ls - mis, mis, crlf_len_hbm(buf, W)};
             auto lu = [&](int) { return L; };
             auto ll = [&](int lend, auto&& f) { f(LineT<const LP_G uint8_t*>{ls - mis, mis, lend}); };
-            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, WC, redo);
+            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, heads, WC, redo);
         }
         __syncthreads();
         WC.store(C, wave);
