@@ -1704,9 +1704,19 @@ __host__ __device__ LP_INLINE void iso_week(int32_t y, int32_t days, int32_t& wy
 
 // Packed local ("as parsed") and UTC calendar fields and epoch seconds of a
 // resolved local date-time (day number `days`) at offset `off` seconds.
-__host__ __device__ LP_INLINE void time_fields(int32_t y, int m, int d, int hh, int mi, int ss, int off, int32_t days,
+// false: the local or the UTC date is past 9999-12-31 (9999-12-31T24:00:00,
+// or a negative offset that moves a 9999-12-31 time to or past the next UTC
+// midnight).  The reference prints a five-digit year its own way
+// (DateTimeFormatter "yyyy", SignStyle.EXCEEDS_PAD), which the engine does not
+// restate: the callers make the line FALLBACK.  One compare of the day number
+// on every other date, and the kernels' registers as they were; the same two
+// tests placed in the branches for 24:00:00 and for a UTC date on another day
+// cost the fixed-shape instances a VGPR (73) and with it a wave per SIMD.
+constexpr int32_t DAYS_9999_12_31 = 2932896;
+__host__ __device__ LP_INLINE bool time_fields(int32_t y, int m, int d, int hh, int mi, int ss, int off, int32_t days,
                                                int64_t& epoch_s, uint64_t& local, uint64_t& utc) {
     const int sod = hh * 3600 + mi * 60 + ss;
+    if (days >= DAYS_9999_12_31 && (days > DAYS_9999_12_31 || sod - off >= 86400)) return false;
     epoch_s = (int64_t)days * 86400 + sod - off;
     int32_t wy;
     int wk;
@@ -1723,14 +1733,17 @@ __host__ __device__ LP_INLINE void time_fields(int32_t y, int m, int d, int hh, 
     }
     utc = pack_cal((uint32_t)y, m, d, (uint32_t)(t / 3600), (uint32_t)(t % 3600 / 60), (uint32_t)(t % 60),
                    (uint32_t)wy, wk);
+    return true;
 }
 
 // DateTimeFormatter "dd/MMM/yyyy:HH:mm:ss ZZ", parseCaseInsensitive,
 // Locale.UK, ResolverStyle.SMART (TimeStampDissector.java:46,100-109,418):
 // day 1..31 clamped to the month length, 24:00:00 = next day 00:00:00,
-// offset sign+HHMM (each <= 59) with |offset| <= 18:00.
+// offset sign+HHMM (each <= 59) with |offset| <= 18:00.  Returns ST_OK,
+// ST_BAD (DateTimeParseException) or ST_FALLBACK (a local or UTC date past
+// year 9999, time_fields).
 template <typename LN>
-__host__ __device__ LP_INLINE bool parse_apache_time(const LN& L, int a, int64_t& epoch_s, uint64_t& local, uint64_t& utc) {
+__host__ __device__ LP_INLINE int parse_apache_time(const LN& L, int a, int64_t& epoch_s, uint64_t& local, uint64_t& utc) {
     const Bytes28 c = load28(L, a);
     int day = (c[0] - '0') * 10 + (c[1] - '0');
     // month name: case-insensitive against the 12 UK short names
@@ -1739,24 +1752,24 @@ __host__ __device__ LP_INLINE bool parse_apache_time(const LN& L, int a, int64_t
     const uint32_t names[12] = {0x6a616e, 0x666562, 0x6d6172, 0x617072, 0x6d6179, 0x6a756e,
                                 0x6a756c, 0x617567, 0x736570, 0x6f6374, 0x6e6f76, 0x646563};
     for (int k = 0; k < 12; ++k) if (names[k] == m3) month = k + 1;
-    if (!month) return false;
+    if (!month) return ST_BAD;
     int hh = (c[12] - '0') * 10 + (c[13] - '0');
     int mi = (c[15] - '0') * 10 + (c[16] - '0');
     int ss = (c[18] - '0') * 10 + (c[19] - '0');
     int off;
     if (c[21] == '+' && c[22] == '0' && c[23] == '0' && c[24] == '0' && c[25] == '0') off = 0;
     else {
-        if (c[21] == '|') return false;
+        if (c[21] == '|') return ST_BAD;
         int oh = (c[22] - '0') * 10 + (c[23] - '0'), om = (c[24] - '0') * 10 + (c[25] - '0');
-        if (oh > 59 || om > 59) return false;
+        if (oh > 59 || om > 59) return ST_BAD;
         off = (c[21] == '-' ? -1 : 1) * (oh * 3600 + om * 60);
     }
-    if (off > 64800 || off < -64800) return false;
-    if (day < 1 || day > 31) return false;
+    if (off > 64800 || off < -64800) return ST_BAD;
+    if (day < 1 || day > 31) return ST_BAD;
     const int32_t year = (int32_t)((c[7] - '0') * 1000 + (c[8] - '0') * 100 + (c[9] - '0') * 10 + (c[10] - '0'));
     int ml = month_len(year, month);
     if (day > ml) day = ml;
-    if (mi > 59) return false;
+    if (mi > 59) return ST_BAD;
     int d = day, m = month;
     int32_t y = year;
     int32_t days = days_from_civil(y, m, d);
@@ -1765,32 +1778,32 @@ __host__ __device__ LP_INLINE bool parse_apache_time(const LN& L, int a, int64_t
         ++days;
         civil_from_days(days, y, m, d);
     } else if (hh > 23 || ss > 59) {
-        return false;
+        return ST_BAD;
     }
-    time_fields(y, m, d, hh, mi, ss, off, days, epoch_s, local, utc);
-    return true;
+    return time_fields(y, m, d, hh, mi, ss, off, days, epoch_s, local, utc) ? ST_OK : ST_FALLBACK;
 }
 
 // TimeStampDissector("TIME.ISO8601", "yyyy-MM-dd'T'HH:mm:ssXXX")
 // (hp/HttpdLoglineParser.java:110, TimeStampDissector.java:100-108) on the
 // 25 bytes at a (the token kind proved the digit / separator layout):
 // SMART resolution as parse_apache_time, numeric month 1..12, offset
-// "+HH:MM" (numbers <= 59, total within +-18:00; '|' fails).
+// "+HH:MM" (numbers <= 59, total within +-18:00; '|' fails).  Returns as
+// parse_apache_time.
 template <typename LN>
-__host__ __device__ LP_INLINE bool parse_iso_time(const LN& L, int a, int64_t& epoch_s, uint64_t& local, uint64_t& utc) {
+__host__ __device__ LP_INLINE int parse_iso_time(const LN& L, int a, int64_t& epoch_s, uint64_t& local, uint64_t& utc) {
     const Bytes28 c = load28(L, a);
     auto d2 = [&](int k) { return (int)(c[k] - '0') * 10 + (int)(c[k + 1] - '0'); };
     const int32_t year = (int32_t)((c[0] - '0') * 1000 + (c[1] - '0') * 100 + (c[2] - '0') * 10 + (c[3] - '0'));
     int month = d2(5), day = d2(8), hh = d2(11), mi = d2(14), ss = d2(17);
-    if (c[19] == '|') return false;
+    if (c[19] == '|') return ST_BAD;
     const int oh = d2(20), om = d2(23);
-    if (oh > 59 || om > 59) return false;
+    if (oh > 59 || om > 59) return ST_BAD;
     const int off = (c[19] == '-' ? -1 : 1) * (oh * 3600 + om * 60);
-    if (off > 64800 || off < -64800) return false;
-    if (month < 1 || month > 12 || day < 1 || day > 31) return false;
+    if (off > 64800 || off < -64800) return ST_BAD;
+    if (month < 1 || month > 12 || day < 1 || day > 31) return ST_BAD;
     const int ml = month_len(year, month);
     if (day > ml) day = ml;
-    if (mi > 59) return false;
+    if (mi > 59) return ST_BAD;
     int32_t y = year;
     int32_t days = days_from_civil(y, month, day);
     if (hh == 24 && mi == 0 && ss == 0) {
@@ -1798,10 +1811,9 @@ __host__ __device__ LP_INLINE bool parse_iso_time(const LN& L, int a, int64_t& e
         ++days;
         civil_from_days(days, y, month, day);
     } else if (hh > 23 || ss > 59) {
-        return false;
+        return ST_BAD;
     }
-    time_fields(y, month, day, hh, mi, ss, off, days, epoch_s, local, utc);
-    return true;
+    return time_fields(y, month, day, hh, mi, ss, off, days, epoch_s, local, utc) ? ST_OK : ST_FALLBACK;
 }
 
 // WeekFields (java.time.temporal.WeekFields.ComputedDayOfField) of the date
@@ -2235,7 +2247,7 @@ __host__ __device__ LP_INLINE int parse_strf_time(const TimeStage& T, const LN& 
     if (dy < 1 || dy > 9999) return ST_FALLBACK;
     LP_PROF(15);
     int64_t es;
-    time_fields(dy, dm, dd, th, tmi, tse, off, days, es, local, utc);
+    if (!time_fields(dy, dm, dd, th, tmi, tse, off, days, es, local, utc)) return ST_FALLBACK;  // UTC past year 9999
     LP_PROF(16);
     epoch_ms = es * 1000 + (int64_t)(nos / 1000000);
     nanos = (uint32_t)nos;
@@ -2780,22 +2792,24 @@ __host__ __device__ LP_INLINE void first_line_stage(const LN& L, LineOut& o, int
 }
 
 // The time and first-line stages of a fixed shape (lp_fixed.h): its stage
-// lists are constants (every time stage TK_APACHE).  false: a time stamp
-// TimeStampDissector rejects (the line is BAD).
+// lists are constants (every time stage TK_APACHE).  Returns ST_OK, or the
+// first failing stage's ST_BAD (a time stamp TimeStampDissector rejects) /
+// ST_FALLBACK (parse_apache_time).
 template <int SHAPE, int T, typename LN>
-__host__ __device__ LP_INLINE void fixed_time_step(const LN& L, LineOut& o, bool& ok) {
+__host__ __device__ LP_INLINE void fixed_time_step(const LN& L, LineOut& o, int& st) {
     constexpr int k = fixed_shape(SHAPE).time_tok[T];
-    if (!ok) return;
+    if (st != ST_OK) return;
     int64_t ep;
     uint64_t lo, ut;
-    if (!parse_apache_time(L, (int)(o.caps.get_u(k) & 0xFFFF), ep, lo, ut)) { ok = false; return; }
+    st = parse_apache_time(L, (int)(o.caps.get_u(k) & 0xFFFF), ep, lo, ut);
+    if (st != ST_OK) return;
     time_store<false>(o, T, ep * 1000, lo, ut, 0);
 }
 template <int SHAPE, typename LN, size_t... J>
-__host__ __device__ LP_INLINE bool fixed_time_stages(const LN& L, LineOut& o, std::index_sequence<J...>) {
-    bool ok = true;
-    (fixed_time_step<SHAPE, (int)J>(L, o, ok), ...);
-    return ok;
+__host__ __device__ LP_INLINE int fixed_time_stages(const LN& L, LineOut& o, std::index_sequence<J...>) {
+    int st = ST_OK;
+    (fixed_time_step<SHAPE, (int)J>(L, o, st), ...);
+    return st;
 }
 template <int SHAPE, int F, typename LN>
 __host__ __device__ LP_INLINE void fixed_fl_step(const LN& L, LineOut& o) {
@@ -2946,8 +2960,9 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
     LP_PROF(5);
     // TimeStampDissector (MULTI: slot s = the s-th stage of the lane's format)
     if constexpr (SHAPE != FS_NONE) {
-        if (!fixed_time_stages<SHAPE>(L, o, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_time>{})) {
-            o.status = ST_BAD;
+        const int st = fixed_time_stages<SHAPE>(L, o, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_time>{});
+        if (st != ST_OK) {
+            o.status = st;
             return;
         }
     } else for (int s = 0; s < P.n_time; ++s) {
@@ -2967,12 +2982,14 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
         int64_t ep; uint64_t lo, ut;
         uint32_t ns = 0;
         if (T.kind == TK_APACHE) {
-            if (!parse_apache_time(L, a, ep, lo, ut)) { o.status = ST_BAD; return; }
+            const int st = parse_apache_time(L, a, ep, lo, ut);
+            if (st != ST_OK) { o.status = st; return; }
             ep *= 1000;
         } else if constexpr (SIMPLE) {
             continue;  // (not in this instance's programs)
         } else if (T.kind == TK_ISO) {
-            if (!parse_iso_time(L, a, ep, lo, ut)) { o.status = ST_BAD; return; }
+            const int st = parse_iso_time(L, a, ep, lo, ut);
+            if (st != ST_OK) { o.status = st; return; }
             ep *= 1000;
         } else {
             // an empty or "-" (null) value has no outputs (TimeStampDissector.java:412-415)

@@ -178,14 +178,7 @@ __global__ __launch_bounds__(64 * CW) void k_table_chars(const DeviceArgs* __res
             }
         }
         if (v.kind == 2) {
-            uint64_t u = v.l < 0 ? 0 - (uint64_t)v.l : (uint64_t)v.l;
-            const uint32_t n = digits(v.l);
-            uint32_t q = n;
-            do {
-                f[--q] = (uint8_t)('0' + u % 10);
-                u /= 10;
-            } while (u);
-            if (v.l < 0) f[0] = '-';
+            write_long(f, v.l, digits(v.l));
             flag = 1;
         } else if (v.kind == 3) {
             for (uint32_t q = 0; q < v.n; ++q) f[q] = (uint8_t)v.buf[q];

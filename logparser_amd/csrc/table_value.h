@@ -9,6 +9,7 @@
 
 #include "kernels.h"
 #include "lp_device.h"
+#include "lp_value.h"  // digits, write_long, parse_long, decimal_to_double
 
 namespace lp {
 
@@ -31,84 +32,6 @@ __constant__ uint8_t MONTH_OFF[13] = {0, 7, 15, 20, 25, 28, 32, 36, 42, 51, 58, 
 __device__ __forceinline__ void put2(char* b, int64_t v) {
     b[0] = (char)('0' + v / 10);
     b[1] = (char)('0' + v % 10);
-}
-
-__device__ __forceinline__ uint32_t digits(int64_t l) {
-    uint64_t u = l < 0 ? 0 - (uint64_t)l : (uint64_t)l;
-    uint32_t n = 1;
-    while (u >= 10) { u /= 10; ++n; }
-    return n + (l < 0 ? 1u : 0u);
-}
-
-__device__ __forceinline__ void write_long(LP_G uint8_t* d, int64_t l, uint32_t n) {  // n = digits(l)
-    uint64_t u = l < 0 ? 0 - (uint64_t)l : (uint64_t)l;
-    uint32_t k = n;
-    do {
-        d[--k] = (uint8_t)('0' + u % 10);
-        u /= 10;
-    } while (u);
-    if (l < 0) d[0] = '-';
-}
-
-// Long.parseLong (the host table's java_parse_long)
-__device__ bool parse_long(const LP_G uint8_t* p, uint32_t n, bool amp, int64_t& out) {
-    if (amp || n == 0) return false;
-    uint32_t k = 0;
-    bool neg = false;
-    if (p[0] == '-' || p[0] == '+') { neg = p[0] == '-'; k = 1; }
-    if (k == n) return false;
-    uint64_t v = 0;
-    for (; k < n; ++k) {
-        const uint32_t d = p[k] - '0';
-        if (d > 9) return false;
-        if (v > (0x8000000000000000ull - d) / 10) return false;  // past 2^63
-        v = v * 10 + d;
-    }
-    if (!neg && v == 0x8000000000000000ull) return false;
-    out = neg ? (int64_t)(0 - v) : (int64_t)v;
-    return true;
-}
-
-// Double.parseDouble of "I.F" (digits '.' digits, each at most 18 digits:
-// a SECOND_MILLIS upstream list item, UpstreamModule's element kind):
-// correctly rounded, as Java's parse (IEEE round half to even).  S = I *
-// 10^f + F and the value is S / 10^f: exact by one IEEE division when S <
-// 2^53 and f <= 22 (both operands exact); else the quotient's 54-55
-// leading bits by binary long division in 128-bit integers (S < 2^120),
-// rounded with the remainder as the sticky bit.
-__device__ double decimal_to_double(const LP_G uint8_t* p, uint32_t n) {
-    typedef unsigned __int128 u128;
-    uint64_t I = 0, F = 0;
-    uint32_t q = 0;
-    int f = 0;
-    for (; q < n && p[q] != '.'; ++q) I = I * 10u + (p[q] - '0');
-    for (++q; q < n; ++q, ++f) F = F * 10u + (p[q] - '0');
-    u128 D = 1;
-    for (int k = 0; k < f; ++k) D *= 10u;
-    const u128 S = (u128)I * D + F;
-    if (S == 0) return 0.0;
-    if (S < ((u128)1 << 53) && f <= 22) return (double)(uint64_t)S / (double)(uint64_t)D;
-    auto bitlen = [](u128 x) {
-        const uint64_t hi = (uint64_t)(x >> 64), lo = (uint64_t)x;
-        return hi ? 128 - __builtin_clzll(hi) : lo ? 64 - __builtin_clzll(lo) : 0;
-    };
-    const int k = 54 - (bitlen(S) - bitlen(D));  // S * 2^k / D in [2^53, 2^55)
-    u128 N = S, Dn = D;
-    if (k >= 0) N <<= k;
-    else Dn <<= -k;
-    uint64_t quo = 0;
-    for (int b = 55; b >= 0; --b) {
-        const u128 t = Dn << b;
-        if (N >= t) {
-            N -= t;
-            quo |= 1ull << b;
-        }
-    }
-    const int shift = quo >= (1ull << 54) ? 2 : 1;  // keep 53 significant bits
-    const uint64_t half = 1ull << (shift - 1), r = quo & ((1ull << shift) - 1);
-    uint64_t m = quo >> shift;
-    if (r > half || (r == half && (N != 0 || (m & 1u)))) ++m;
-    return ldexp((double)m, shift - k);
 }
 
 // ResponseSetCookieDissector.dissect (dissectors/ResponseSetCookieDissector.java:86-135) on one
@@ -226,16 +149,20 @@ __device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, c
             v.n = MONTH_OFF[MO] - MONTH_OFF[MO - 1];
             for (uint32_t k = 0; k < v.n; ++k) v.buf[k] = MONTH_TEXT[MONTH_OFF[MO - 1] + k];
             break;
-        case TF_DATE:  // "%04d-%02d-%02d"
+        case TF_DATE: {  // "%04d-%02d-%02d", as Plan::replay prints it: a packed year past 9999 (none comes
+            // from the parse kernels: time_fields sends such a line to FALLBACK) takes five digits
+            const uint32_t o = Y > 9999 ? 1u : 0u;
             v.kind = 3;
-            v.n = 10;
-            put2(v.buf, Y / 100);
-            put2(v.buf + 2, Y % 100);
-            v.buf[4] = '-';
-            put2(v.buf + 5, MO);
-            v.buf[7] = '-';
-            put2(v.buf + 8, D);
+            v.n = 10 + o;
+            v.buf[0] = (char)('0' + Y / 10000);
+            put2(v.buf + o, Y / 100 % 100);
+            put2(v.buf + o + 2, Y % 100);
+            v.buf[o + 4] = '-';
+            put2(v.buf + o + 5, MO);
+            v.buf[o + 7] = '-';
+            put2(v.buf + o + 8, D);
             break;
+        }
         case TF_TIME:  // "%02d:%02d:%02d"
             v.kind = 3;
             v.n = 8;
