@@ -3427,16 +3427,20 @@ __host__ __device__ LP_INLINE QPrep query_prep(const LN& L, uint64_t t0) {
 // escapes, never decoded; a piece without '=' has value ""; else the value
 // goes through Utils.resilientUrlDecode.  A: the piece's spilled bytes
 // (q.need of them, A.used 4-byte aligned, offsets relative to the owning
-// line's region `region`); slot: the piece's table slot.  Returns the arena
-// bytes written.
+// line's region `region`); slot: the piece's table slot.
+// The name part, query_name: the name's ref (a rewritten name is written at
+// A.used, which is left 4-byte aligned after it: where a decoded value
+// starts) and whether the piece is requested.  The value part is
+// query_value_plain, or url_decode_value for a value that holds a '%' / '+'
+// (qp.pv).  query_finish does both for one piece; the URI kernel's piece pass
+// (uri.hip uri_wave) runs the name part where the piece is and hands the
+// values to decode to lanes of their own.
 template <typename LN>
-__host__ __device__ LP_INLINE uint32_t query_finish(const Program& P, const QueryStage& Q, const LN& L, Arena& A,
-                                                    const LP_G uint8_t* region, LP_G uint64_t* slot, const QPrep& qp) {
+__host__ __device__ LP_INLINE bool query_name(const Program& P, const QueryStage& Q, const LN& L, Arena& A,
+                                              const LP_G uint8_t* region, const QPrep& qp, uint64_t& nref) {
     const int s = qp.s, e = qp.e, eq = qp.eq;
     const int ne = eq >= 0 ? eq : e;
-    const uint32_t a1 = A.used;
     // name [s, ne): URIUtil-escaped and lower-cased as in the rawQuery
-    uint64_t nref;
     if (qp.rw) {
         const char* HX = "0123456789abcdef";  // URIUtil's %XX, lower-cased with the name
         const uint32_t mark = A.used;
@@ -3462,15 +3466,26 @@ __host__ __device__ LP_INLINE uint32_t query_finish(const Program& P, const Quer
         }
         want = same;
     }
-    if (!want) {
+    return want;
+}
+// the value of a piece that needs no decoding (!qp.pv)
+template <typename LN>
+__host__ __device__ LP_INLINE uint64_t query_value_plain(const LN& L, const QPrep& qp) {
+    if (qp.eq < 0) return mkref(0, 0, false);  // no '=' -> ""
+    return src_ref(L, qp.eq + 1, qp.e - qp.eq - 1);
+}
+// Returns the arena bytes written.
+template <typename LN>
+__host__ __device__ LP_INLINE uint32_t query_finish(const Program& P, const QueryStage& Q, const LN& L, Arena& A,
+                                                    const LP_G uint8_t* region, LP_G uint64_t* slot, const QPrep& qp) {
+    const uint32_t a1 = A.used;
+    uint64_t nref;
+    if (!query_name(P, Q, L, A, region, qp, nref)) {
         slot[0] = REF_SKIP;
         slot[1] = 0;
         return A.used - a1;
     }
-    uint64_t vref;
-    if (eq < 0) vref = mkref(0, 0, false);  // no '=' -> ""
-    else if (!qp.pv) vref = src_ref(L, eq + 1, e - eq - 1);
-    else vref = url_decode_value(L, eq + 1, e, A);
+    const uint64_t vref = qp.pv ? url_decode_value(L, qp.eq + 1, qp.e, A) : query_value_plain(L, qp);
     slot[0] = nref;
     slot[1] = vref;
     return A.used - a1;

@@ -274,6 +274,68 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
     }
 }
 
+// Query values waiting for the piece pass's dense decode (uri_wave): a piece
+// whose value holds a '%' / '+' is decoded by a lane of its own, not by the
+// lane that holds the piece.  That lane posts a descriptor -- the value's
+// source bytes [S, E) as offsets from its view's base, where the output
+// starts in the owning line's region (used), that region (reg: its offset
+// from the wave's first region) and the piece's table slot in it (soff) --
+// and lane d of a decode pass takes descriptor d.  A piece whose value holds
+// a '%' / '+' but is not decoded (its name is not requested, or its spill did
+// not fit) posts an empty descriptor: a block's descriptors are numbered
+// before its names are looked at.  URI_CAPD descriptors fit the buffer: one
+// pass' worth, and any one block's.  A view in LDS (the compact buffer, one
+// base for the wave) takes 16 bytes, a view in HBM carries its line's base
+// pointer and takes 32.
+constexpr int URI_CAPD = PW;
+constexpr uint32_t QDESC_NONE = ~0u;  // soff of an empty descriptor
+template <typename LN>
+struct QDescs {
+    static constexpr int WORDS = LN::has_masks ? 2 : 4;  // uint64_t per descriptor
+    uint64_t* buf;  // 16-byte aligned, URI_CAPD * WORDS words
+    __device__ __forceinline__ void post(uint32_t d, const LN& OL, int vs, int e, uint32_t used, uint32_t reg,
+                                         uint32_t soff) const {
+        const uint32_t S = OL.o + (uint32_t)vs, E = OL.o + (uint32_t)e;
+        u32x4* q = reinterpret_cast<u32x4*>(buf + WORDS * d);
+        if constexpr (LN::has_masks) {
+            q[0] = u32x4{S | E << 16, used, reg, soff};  // (S <= E <= 0xFFFF: the compact buffers are smaller)
+        } else {
+            const unsigned long long b = (unsigned long long)(uintptr_t)OL.b;
+            q[0] = u32x4{S, E, reg, soff};
+            q[1] = u32x4{(uint32_t)b, (uint32_t)(b >> 32), used, 0u};
+        }
+    }
+    __device__ __forceinline__ void post_none(uint32_t d) const {
+        *reinterpret_cast<u32x4*>(buf + WORDS * d) = u32x4{0u, 0u, 0u, QDESC_NONE};
+    }
+    // Descriptor d: V views the value's bytes [S, E) (V.o = 0; the view ends
+    // with the value, whose decoder reads no word that starts at or after E:
+    // every escape of a piece lies inside it).  L0: any view of the wave's
+    // (the LDS base).  false: an empty descriptor.
+    __device__ __forceinline__ bool take(uint32_t d, const LN& L0, LN& V, int& S, int& E, uint32_t& used, uint32_t& reg,
+                                         uint32_t& soff) const {
+        const u32x4* q = reinterpret_cast<const u32x4*>(buf + WORDS * d);
+        const u32x4 a = q[0];
+        V = L0;
+        V.o = 0;
+        reg = a[2];
+        soff = a[3];
+        if constexpr (LN::has_masks) {
+            S = (int)(a[0] & 0xFFFFu);
+            E = (int)(a[0] >> 16);
+            used = a[1];
+        } else {
+            const u32x4 c = q[1];
+            V.b = reinterpret_cast<decltype(V.b)>((uintptr_t)((unsigned long long)c[0] | (unsigned long long)c[1] << 32));
+            S = (int)a[0];
+            E = (int)a[1];
+            used = c[2];
+        }
+        V.n = E;
+        return soff != QDESC_NONE;
+    }
+};
+
 // Phase 2, the arena allocation and the query pieces of one wave; lu(u) is
 // the lane's line view of URI stage u (valid for every lane, empty stages
 // included: the query pass reads other lanes' views).
@@ -283,10 +345,15 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
 // A line whose URI the reference repairs (ST_REPAIR) is stored as FALLBACK;
 // QUEUE: it is appended to uri_fix_list (k_uri_lines), else `redo` tells the
 // caller to redo it (k_uri_overflow, which also works the list off).
+// scratch: LDS for the piece pass's descriptors (QDescs), the kernels' UEV
+// plane: the walks and uri_stage_rest are its last readers (nothing after
+// LP_PROF(21) calls a view's mask(): query_prep, query_name and
+// url_decode_value read bytes and words only), and the direct path never
+// reads it.
 template <int NU, int NQ, bool COOP, bool SLOT, bool QUEUE, typename LU, typename LL>
 __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, UriLane<NU>& U, LU&& lu, LL&& ll,
-                                         bool active, int64_t li, int64_t wave, uint64_t* heads, WaveCounts& WC,
-                                         bool& redo) {
+                                         bool active, int64_t li, int64_t wave, uint64_t* heads, uint64_t* scratch,
+                                         WaveCounts& WC, bool& redo) {
     const int lane = lane_id();
     const int nq = P.n_query < NQ ? P.n_query : NQ;
     uint32_t need = 0;
@@ -321,7 +388,8 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
     // regions start 16-byte aligned (their query tables take 16-byte slot
     // stores; spills keep the bump pointer only 4-byte aligned)
     if (lane == 63 && total) wbase = atomicAdd(&C.meta->shard_top[16 * shard], (unsigned long long)total + 12ull);
-    wbase = (__shfl(wbase, 63) + 15) & ~15ull;
+    // (read as scalars: the wave's base is kept for the piece pass's descriptors)
+    wbase = (((unsigned long long)lane_value((uint32_t)wbase, 63) | (unsigned long long)lane_value((uint32_t)(wbase >> 32), 63) << 32) + 15) & ~15ull;
     const bool fits = wbase + total <= C.shard_cap;
     LP_PROF(26);
     uint32_t written = 0;
@@ -404,7 +472,8 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
     // pieces of every query stage in one numbering (a lane's stage-0 pieces,
     // then its stage-1 pieces, ...), QR blocks of 64 pieces per round: their
     // table slots loaded together, then query_prep, ONE spill allocation for
-    // the round, query_finish.  Most waves need one round for all stages.
+    // the round, query_finish's name part where the piece is and its decode
+    // on dense lanes.  Most waves need one round for all stages.
     if (nq > 0) {
         constexpr int QR = LP_URI_QR;
         __syncthreads();  // the table slots written in phase 2 are visible to every lane
@@ -439,6 +508,32 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
                 if (pq == qs) OL = V;
             }
             return OL;
+        };
+        // The dense decode pass: lane d decodes the d-th waiting value
+        // (url_decode_value, as query_finish runs it: the same bytes, the
+        // last word's padding included) and stores its ref in the piece's
+        // slot.  Every owner is a line of this wave: its region lies at reg
+        // after the wave's first.  Wave-uniform control flow; workgroups are
+        // one wave, the barriers only order the LDS accesses.
+        typedef decltype(lu(0)) QL;
+        const QDescs<QL> QD{scratch};
+        const unsigned long long w0 = (unsigned long long)shard * C.shard_cap + wbase;  // the wave's first region
+        LP_G uint8_t* const wreg = C.arena + w0;
+        auto decode_waiting = [&](uint32_t n) {
+            LP_PT_DECL
+            __syncthreads();  // the descriptors posted are visible
+            if ((uint32_t)lane < n) {
+                QL V;
+                int S, E;
+                uint32_t used, reg, soff;
+                if (QD.take((uint32_t)lane, lu(P.query[0].uri), V, S, E, used, reg, soff)) {
+                    Arena A{wreg + reg, used, used};
+                    reinterpret_cast<LP_G uint64_t*>(wreg + reg + soff)[1] = url_decode_value(V, S, E, A);
+                    written += A.used - used;
+                }
+            }
+            __syncthreads();  // ... and read before the next are posted
+            LP_PACC(57);
         };
         for (uint32_t g0 = 0; g0 < tot; g0 += QR * PW) {
             int own[QR], pqs[QR];
@@ -480,10 +575,26 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
             if (lane == 63 && rtot) rbase = atomicAdd(&C.meta->shard_top[16 * shard], (unsigned long long)rtot);
             unsigned long long at = __shfl(rbase, 63) + x - mine;  // this lane's first piece in the shard
             LP_PROF(19);
+            // query_finish, in two parts: the lane that holds a piece does the
+            // name part (query_name) and the values that need no decoding; a
+            // piece whose value does (qp.pv) it posts for the dense decode
+            // pass, at its rank among the block's such pieces after those
+            // already waiting.  Waiting values are decoded when a block's
+            // would not fit with them, and after the round's last block.
+            uint32_t nwait = 0;  // (wave-uniform)
 #pragma unroll
             for (int k = 0; k < QR; ++k) {
                 if (g0 + (uint32_t)(k * PW) >= tot) continue;
                 const uint32_t g = g0 + (uint32_t)(k * PW + lane);
+                const bool pv = g < tot && qp[k].pv;
+                const uint64_t PB = __ballot(pv);
+                const uint32_t nb = (uint32_t)__popcll(PB);
+                if (nwait + nb > (uint32_t)URI_CAPD) {
+                    decode_waiting(nwait);
+                    nwait = 0;
+                }
+                const uint32_t d = nwait + __builtin_amdgcn_mbcnt_hi((uint32_t)(PB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)PB, 0u));
+                nwait += nb;
                 const int ow = own[k];
                 const unsigned long long oab = __shfl(my_ab, ow);
                 const auto OL = owner_view(ow, pqs[k]);
@@ -495,10 +606,23 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
                         slot[0] = REF_SKIP;
                         slot[1] = 0;
                         povf = true;
+                        if (pv) QD.post_none(d);
                         atomicAdd(&C.meta->arena_ovf, 1ull);  // the batch is re-run with a larger arena
                     } else {
                         Arena A{C.arena + oab, (uint32_t)(at - rel), (uint32_t)(at - rel + qp[k].need)};
-                        written += query_finish(P, P.query[pqs[k]], OL, A, C.arena + oab, slot, qp[k]);
+                        const uint32_t a1 = A.used;
+                        uint64_t nref;
+                        const bool want = query_name(P, P.query[pqs[k]], OL, A, C.arena + oab, qp[k], nref);
+                        if (!want) {
+                            slot[0] = REF_SKIP;
+                            slot[1] = 0;
+                        } else {
+                            slot[0] = nref;
+                            if (!pv) slot[1] = query_value_plain(OL, qp[k]);
+                        }
+                        // (A.used: after the aligned name part, where the value's output starts)
+                        if (pv) QD.post(d, OL, qp[k].eq + 1, qp[k].e, A.used, (uint32_t)(oab - w0), want ? soffs[k] : QDESC_NONE);
+                        written += A.used - a1;
                     }
                     at += qp[k].need;
                 }
@@ -507,6 +631,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
                 // are spent, delivered with those lines FALLBACK)
                 for (uint64_t m = __ballot(povf); m; m &= m - 1) piece_ovf |= 1ull << __shfl(ow, (int)__builtin_ctzll(m));
             }
+            if (nwait) decode_waiting(nwait);
         }
         if (((piece_ovf >> lane) & 1) && o.status == ST_OK) o.status = ST_FALLBACK;
     }
@@ -658,7 +783,7 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
         if (lin) f(LineT<lds_bytes>{(lds_bytes)cbuf, lorig, lend});
         else f(LineT<const LP_G uint8_t*>{lsp - lmis, lmis, lend});
     };
-    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, heads, WC, redo);
+    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, heads, plane, WC, redo);
     return true;
 }
 
@@ -676,7 +801,9 @@ __global__ __launch_bounds__(PW, SLOT ? LP_URI_SLOT_WPE : 4) void k_uri_lines(co
     const int64_t wave = blockIdx.x;
     if (wave * PW >= n_lines || C.meta->cap_ovf) return;
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP / 4 + 16];
-    __shared__ uint64_t plane[URI_CAP / 64 + 1];
+    // (the UEV plane, then the piece pass's descriptors: 16-byte stores)
+    __shared__ __attribute__((aligned(16))) uint64_t plane[URI_CAP / 64 + 1];
+    static_assert(sizeof(plane) >= URI_CAPD * 16, "the plane holds URI_CAPD descriptors of the compact view");
     __shared__ uint64_t heads[OWNER_LDS_WORDS];  // (with cbuf and plane within 10,240 B: 16 workgroups per CU)
     WaveCounts WC;
     bool redo;  // (unused: this kernel queues such lines)
@@ -775,7 +902,8 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
     const uint64_t nq = C.meta->uri_ovf_waves;
     const uint64_t nfix = min((uint64_t)(uint32_t)C.meta->uri_fix_lines, (uint64_t)C.cap_lines);
     __shared__ __attribute__((aligned(16))) uint32_t cbuf[URI_CAP_OVF / 4 + 16];
-    __shared__ uint64_t plane[URI_CAP_OVF / 64 + 1];
+    __shared__ __attribute__((aligned(16))) uint64_t plane[URI_CAP_OVF / 64 + 1];
+    static_assert(sizeof(plane) >= URI_CAPD * 32 && URI_CAP_OVF + 64 <= 0xFFFF, "URI_CAPD descriptors of either view; 16-bit offsets");
     __shared__ uint64_t heads[OWNER_LDS_WORDS];
     for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
         const int64_t wave = C.uri_ovf_list[q];
@@ -789,7 +917,7 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
             const LineT<const LP_G uint8_t*> L{ls - mis, mis, crlf_len_hbm(buf, W)};
             auto lu = [&](int) { return L; };
             auto ll = [&](int lend, auto&& f) { f(LineT<const LP_G uint8_t*>{ls - mis, mis, lend}); };
-            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, heads, WC, redo);
+            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, heads, plane, WC, redo);
         }
         __syncthreads();
         WC.store(C, wave);

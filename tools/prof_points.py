@@ -71,6 +71,13 @@ for order in orders:
     rows = [r for r in T if r[order[0]] and r[order[-1]]]
     if rows:
         print("  kernel total %.0f cycles per wave" % np.mean([r[order[-1]] - r[order[0]] for r in rows]))
+# accumulating slots (LP_PACC): cycles summed over the passes of a loop, inside the stage named
+ACC = {57: ("q values decoded", "q spill allocated -> query pieces")}
+for k, (nm, inside) in ACC.items():
+    rows = T[:, 22] != 0
+    if rows.any():
+        print("  %-18s %9.0f cycles/wave  (inside %s; %d waves, %d with a pass)"
+              % (nm, T[rows, k].mean(), inside, int(rows.sum()), int((T[rows, k] != 0).sum())))
 
 # first-leaf match cycles per element (LP_PROF_EL, slots 64 + i), k_parse_lines waves
 el = T[:, 64:96]
