@@ -140,6 +140,32 @@ class EngineUnavailable(RuntimeError):
     """The HIP library or a GPU is missing."""
 
 
+# What a table call's code other than LP_OK raises, per family: code -> (exception, message);
+# None: every other code (its message takes the code)
+_SELECT_ERRORS = {None: (ValueError, "lp_result_select failed: %d")}
+_TABLE_FROM_ERRORS = {None: (ValueError, "lp_result_table failed: %d")}
+_TABLE_DEVICE_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use table_from"),
+                        None: (ValueError, "lp_result_table (device) failed: %d")}
+_DICT_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use table_dict_from"),
+                None: (ValueError, "lp_result_table_dict failed: %d")}
+_MAP_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a map column's members are derived on the host only: use table_map_from"),
+               LP_E_MISSING: (MissingDissectorsException, "lp_result_table_map: a path the parser does not deliver"),
+               None: (ValueError, "lp_result_table_map failed: %d")}
+
+
+def _sized_call(call, grow, errors):
+    """The size protocol of the table calls: call() with the buffers at hand;
+    on LP_E_NOMEM grow() makes what the reported lengths ask for and call()
+    runs once more.  Any code but LP_OK then raises what errors (above) names."""
+    rc = call()
+    if rc == LP_E_NOMEM:
+        grow()
+        rc = call()
+    if rc != LP_OK:
+        exc, msg = errors.get(rc) or errors[None]
+        raise exc(msg % rc if rc not in errors else msg)
+
+
 _lib = None
 
 
@@ -408,21 +434,42 @@ class BatchResult:
             raise ValueError("rows: a contiguous int64 numpy array expected")
         return rows.ctypes.data, int(rows.size)
 
+    def _window(self, rows, first, count, device):
+        """(rows_p, first, count) of a table call: the window [first,
+        first+count) (count None: up to the last line), or the row list"""
+        if rows is not None:
+            rows_p, n_rows = self._rows_arg(rows, first, count, device)
+            return rows_p, 0, n_rows
+        return None, first, self.n_lines - first if count is None else count
+
+    def _entry(self, family, res, rows_p, first, count, cols, n_cols, threads):
+        """the call of lp_result_<family> (rows_p None) or of lp_result_<family>_rows"""
+        L, h = lib(), self._p._h
+        if rows_p is None:
+            fn = getattr(L, "lp_result_" + family)
+            return lambda: fn(h, ctypes.byref(res), first, count, cols, n_cols, threads)
+        fn = getattr(L, "lp_result_%s_rows" % family)
+        return lambda: fn(h, ctypes.byref(res), rows_p, count, cols, n_cols, threads)
+
+    def _timing(self, lo, hi):
+        """lp_last_timing [lo, hi): HIP-event ms of the last device calls"""
+        t = (ctypes.c_float * hi)()
+        lib().lp_last_timing(self._p._h, t, hi)
+        return t[lo:hi]
+
     def _select(self, res, mask, first, count, alloc, ptr):
         """lp_result_select with the table's size protocol: one call that
         reports the count, one that fills"""
         count = self.n_lines - first if count is None else count
         L = lib()
         n = ctypes.c_uint64(0)
-        rc = L.lp_result_select(self._p._h, ctypes.byref(res), first, count, mask, None, 0, ctypes.byref(n))
-        if rc not in (LP_OK, LP_E_NOMEM):
-            raise ValueError("lp_result_select failed: %d" % rc)
-        rows = alloc(int(n.value))
-        if n.value:
-            rc = L.lp_result_select(self._p._h, ctypes.byref(res), first, count, mask, ptr(rows), n.value, ctypes.byref(n))
-            if rc != LP_OK:
-                raise ValueError("lp_result_select failed: %d" % rc)
-        return rows
+        got = []  # the rows, once the count is known
+
+        def call():
+            return L.lp_result_select(self._p._h, ctypes.byref(res), first, count, mask, ptr(got[0]) if got else None,
+                                      n.value if got else 0, ctypes.byref(n))
+        _sized_call(call, lambda: got.append(alloc(int(n.value))), _SELECT_ERRORS)
+        return got[0] if got else alloc(0)
 
     def select_device(self, mask, first=0, count=None):
         """lp_result_select on the device view: the lines of [first,
@@ -440,9 +487,7 @@ class BatchResult:
 
     def select_timing(self):
         """HIP-event ms of the last device lp_result_select (both passes, the scan, the host's read of the count)"""
-        t = (ctypes.c_float * 12)()
-        lib().lp_last_timing(self._p._h, t, 12)
-        return t[11]
+        return self._timing(11, 12)[0]
 
     def table_from(self, res, columns, first=0, count=None, threads=16, decode=True, rows=None):
         """lp_result_table: typed columns of rows [first, first+count) from a
@@ -454,10 +499,7 @@ class BatchResult:
         for "@line", whose text is not validated UTF-8; decode=False: the
         Arrow pair (offsets, chars bytes) as numpy arrays), a numpy int64 /
         float64 array for BIGINT / DOUBLE ones."""
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, False)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, False)
         kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
         cols = (LpTableCol * len(columns))()
         keep = []
@@ -470,20 +512,13 @@ class BatchResult:
             f64 = np.zeros(max(1, count), dtype=np.float64)
             c.valid, c.i64, c.f64 = valid.ctypes.data, i64.ctypes.data, f64.ctypes.data
             keep.append((valid, i64, f64))
-        L = lib()
-        call = (lambda: L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), threads)) \
-            if rows is None else \
-            (lambda: L.lp_result_table_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(columns), threads))
-        rc = call()
-        if rc == LP_E_NOMEM:
+        def grow():
             for k in range(len(columns)):
                 if cols[k].kind == CAST_STRING:
                     buf = np.zeros(max(1, cols[k].chars_len), dtype=np.uint8)
                     keep[k] = keep[k] + (buf,)
                     cols[k].chars, cols[k].chars_cap = buf.ctypes.data, buf.nbytes
-            rc = call()
-        if rc != LP_OK:
-            raise ValueError("lp_result_table failed: %d" % rc)
+        _sized_call(self._entry("table", res, rows_p, first, count, cols, len(columns), threads), grow, _TABLE_FROM_ERRORS)
         out = {}
         for k, (path, typ) in enumerate(columns):
             valid, i64, f64 = keep[k][:3]
@@ -533,16 +568,9 @@ class BatchResult:
         chars_cap: bytes allotted per STRING column (default: enough after a
         first call that reports the need); buffers: table_buffers(...) to
         fill instead of fresh ones."""
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, True)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, True)
         kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
-        L = lib()
         res = self._view()
-        call = (lambda: L.lp_result_table(self._p._h, ctypes.byref(res), first, count, cols, len(columns), 0)) \
-            if rows is None else \
-            (lambda: L.lp_result_table_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(columns), 0))
         cols = (LpTableCol * len(columns))()
         keep = buffers if buffers is not None else self.table_buffers(columns, count, chars_cap)
         for k, (path, typ) in enumerate(columns):
@@ -556,19 +584,14 @@ class BatchResult:
             if chars is not None:
                 c.chars = chars.data_ptr()
                 c.chars_cap = chars.numel() if (chars_cap or buffers is not None) else 0
-        rc = call()
-        if rc == LP_E_NOMEM:
+        def grow():
             import torch
             dev = torch.device("cuda", self._p.device)
             for k, (path, typ) in enumerate(columns):
                 if typ is str and cols[k].chars_len > cols[k].chars_cap:
                     keep[k][3] = torch.empty(max(1, cols[k].chars_len), dtype=torch.uint8, device=dev)
                     cols[k].chars, cols[k].chars_cap = keep[k][3].data_ptr(), keep[k][3].numel()
-            rc = call()
-        if rc == LP_E_UNSUPPORTED:
-            raise FallbackRequired("a column's values are derived on the host only: use table_from")
-        if rc != LP_OK:
-            raise ValueError("lp_result_table (device) failed: %d" % rc)
+        _sized_call(self._entry("table", res, rows_p, first, count, cols, len(columns), 0), grow, _TABLE_DEVICE_ERRORS)
         out = {}
         for k, (path, typ) in enumerate(columns):
             valid, i64, f64, chars = keep[k]
@@ -581,15 +604,12 @@ class BatchResult:
     def table_timing(self):
         """HIP-event ms of the last device lp_result_table's phases:
         {"values": k_table_values, "scans": offset scans, "chars": k_table_chars}"""
-        t = (ctypes.c_float * 8)()
-        lib().lp_last_timing(self._p._h, t, 8)
-        return {"values": t[5], "scans": t[6], "chars": t[7]}
+        return dict(zip(("values", "scans", "chars"), self._timing(5, 8)))
 
     def _dict_call(self, res, paths, first, count, rows_p, threads, bufs, alloc, ptr):
         """lp_result_table_dict / _rows into bufs (per path [valid, index,
         dict_off, dict_chars]); after LP_E_NOMEM the dictionary's arrays are
         replaced by ones of the reported sizes and the call repeated once"""
-        L = lib()
         cols = (LpTableDictCol * len(paths))()
         for k, path in enumerate(paths):
             c = cols[k]
@@ -597,11 +617,8 @@ class BatchResult:
             valid, index, doff, dchars = bufs[k]
             c.valid, c.index, c.dict_off, c.dict_chars = ptr(valid), ptr(index), ptr(doff), ptr(dchars)
             c.dict_cap, c.dict_chars_cap = len(doff) - 1, len(dchars)
-        call = (lambda: L.lp_result_table_dict(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)) \
-            if rows_p is None else \
-            (lambda: L.lp_result_table_dict_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(paths), threads))
-        rc = call()
-        if rc == LP_E_NOMEM:
+
+        def grow():
             for k in range(len(paths)):
                 c = cols[k]
                 if c.dict_len > c.dict_cap:
@@ -610,11 +627,7 @@ class BatchResult:
                 if c.dict_chars_len > c.dict_chars_cap:
                     bufs[k][3] = alloc(max(1, c.dict_chars_len), "uint8")
                     c.dict_chars, c.dict_chars_cap = ptr(bufs[k][3]), len(bufs[k][3])
-            rc = call()
-        if rc == LP_E_UNSUPPORTED:
-            raise FallbackRequired("a column's values are derived on the host only: use table_dict_from")
-        if rc != LP_OK:
-            raise ValueError("lp_result_table_dict failed: %d" % rc)
+        _sized_call(self._entry("table_dict", res, rows_p, first, count, cols, len(paths), threads), grow, _DICT_ERRORS)
         return {path: (bufs[k][1][:count], (bufs[k][2][:cols[k].dict_len + 1], bufs[k][3][:cols[k].dict_chars_len]),
                        bufs[k][0][:count]) for k, path in enumerate(paths)}
 
@@ -648,10 +661,7 @@ class BatchResult:
         room allotted per column (default: none, the call is repeated once
         with the sizes the first reports); buffers: table_dict_buffers(...)."""
         import torch
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, True)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, True)
         dev = torch.device("cuda", self._p.device)
         dt = {"int64": torch.int64, "uint8": torch.uint8}
         bufs = buffers if buffers is not None else self.table_dict_buffers(columns, count, dict_cap, dict_chars_cap)
@@ -661,10 +671,7 @@ class BatchResult:
     def table_dict_from(self, res, columns, first=0, count=None, threads=16, rows=None):
         """lp_result_table_dict from a host copy: the same arrays as
         table_dict_device, as numpy arrays (bit-identical to the device's)"""
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, False)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, False)
         bufs = [[np.zeros(max(1, count), dtype=np.uint8), np.zeros(max(1, count), dtype=np.int32),
                  np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.uint8)] for _ in columns]
         for b in bufs:
@@ -676,9 +683,7 @@ class BatchResult:
         """HIP-event ms of the last device lp_result_table_dict's phases, summed over its columns:
         {"values": k_table_values of the rows, "insert": table reset + k_dict_insert,
         "index": k_dict_mark + rank scan + k_dict_index, "dict": the dictionary's values}"""
-        t = (ctypes.c_float * 16)()
-        lib().lp_last_timing(self._p._h, t, 16)
-        return {"values": t[12], "insert": t[13], "index": t[14], "dict": t[15]}
+        return dict(zip(("values", "insert", "index", "dict"), self._timing(12, 16)))
 
     def _map_call(self, res, paths, first, count, threads, alloc, bufs, rows_p=None):
         """lp_result_table_map with lp_result_table's size protocol: a first
@@ -698,12 +703,8 @@ class BatchResult:
                 c.entries_cap = min(size(b["key_off"]), size(b["val_off"])) - 1
                 c.key_chars_cap, c.val_chars_cap = size(b["key_chars"]), size(b["val_chars"])
         bind()
-        L = lib()
-        call = (lambda: L.lp_result_table_map(self._p._h, ctypes.byref(res), first, count, cols, len(paths), threads)) \
-            if rows_p is None else \
-            (lambda: L.lp_result_table_map_rows(self._p._h, ctypes.byref(res), rows_p, count, cols, len(paths), threads))
-        rc = call()
-        if rc == LP_E_NOMEM:
+
+        def grow():
             for k in range(len(paths)):
                 c, b = cols[k], bufs[k]
                 if c.entries_len > c.entries_cap:
@@ -713,13 +714,7 @@ class BatchResult:
                 if c.val_chars_len > c.val_chars_cap:
                     b["val_chars"] = alloc(c.val_chars_len, np.uint8)
             bind()
-            rc = call()
-        if rc == LP_E_UNSUPPORTED:
-            raise FallbackRequired("a map column's members are derived on the host only: use table_map_from")
-        if rc == LP_E_MISSING:
-            raise MissingDissectorsException("lp_result_table_map: a path the parser does not deliver")
-        if rc != LP_OK:
-            raise ValueError("lp_result_table_map failed: %d" % rc)
+        _sized_call(self._entry("table_map", res, rows_p, first, count, cols, len(paths), threads), grow, _MAP_ERRORS)
         out = {}
         for k, path in enumerate(paths):
             c, b = cols[k], bufs[k]
@@ -737,10 +732,7 @@ class BatchResult:
         with decode=False {path: {name: numpy array}} (MAP_ARRAYS).  rows (a
         numpy int64 array, not together with first / count): row k is line
         rows[k] (lp_result_table_map_rows)."""
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, False)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, False)
         alloc = lambda n, dt: np.zeros(max(1, n), dtype=dt)
         bufs = [{"valid": alloc(count, np.uint8), "entry_off": alloc(count + 1, np.int64), "key_off": alloc(1, np.int64),
                  "val_off": alloc(1, np.int64), "key_chars": np.zeros(0, np.uint8), "val_chars": np.zeros(0, np.uint8)}
@@ -773,10 +765,7 @@ class BatchResult:
         on the device, not together with first / count): row k is line
         rows[k] (lp_result_table_map_rows)."""
         import torch
-        rows_p = None
-        if rows is not None:
-            rows_p, count = self._rows_arg(rows, first, count, True)
-        count = self.n_lines - first if count is None else count
+        rows_p, first, count = self._window(rows, first, count, True)
         res = self._view()
         dev = torch.device("cuda", self._p.device)
         tdt = {np.int64: torch.int64, np.uint8: torch.uint8}
@@ -791,9 +780,7 @@ class BatchResult:
         """HIP-event ms of the last device lp_result_table_map, summed over
         its columns: {"count": k_map_count and the piece-base scan, "entries":
         k_map_entries and its scans, "fill": k_map_fill and k_map_chars}"""
-        t = (ctypes.c_float * 11)()
-        lib().lp_last_timing(self._p._h, t, 11)
-        return {"count": t[8], "entries": t[9], "fill": t[10]}
+        return dict(zip(("count", "entries", "fill"), self._timing(8, 11)))
 
     def record_json_from(self, res, i):
         """lp_result_record_json: the record of line i from a host copy."""

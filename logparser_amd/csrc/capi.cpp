@@ -71,6 +71,61 @@ struct ColSpec {
     int uri;  // written by the URI kernels (1) or the parse kernels (0): lp_last_bytes' per-kernel split
 };
 
+// The host tables' worker split: [0, count) in T chunks of per rows, the
+// trailing ones empty when T does not divide count or exceeds it; chunk t is
+// [at[t], at[t + 1]).
+struct Chunks {
+    int T;
+    std::vector<int64_t> at;
+    Chunks(int64_t count, int threads) : T(std::max(1, std::min(threads, 64))), at((size_t)T + 1) {
+        const int64_t per = (count + T - 1) / T;
+        for (int t = 0; t <= T; ++t) at[(size_t)t] = std::min(count, t * per);
+    }
+    // fn(t, a, b) for every chunk, one thread each (chunk 0 on the caller's)
+    template <class F>
+    void run(F fn) const {
+        std::vector<std::thread> pool;
+        for (int t = 1; t < T; ++t) pool.emplace_back([&, t] { fn(t, at[(size_t)t], at[(size_t)t + 1]); });
+        fn(0, at[0], at[1]);
+        for (auto& th : pool) th.join();
+    }
+};
+
+// HIP-event times of a device call's phases, over the handle's one pool of
+// table events (a handle's calls are serialised on its stream).  Asking HIP for
+// the time between events of which one was not recorded in this call leaves
+// hipErrorInvalidHandle behind, which the next launch's hipGetLastError takes
+// for its own (an empty table once failed the next lp_parse_batch that way):
+// elapsed() answers 0 for those without asking.
+struct PhaseTimer {
+    hipEvent_t* ev;
+    hipStream_t s;
+    bool on[6] = {false, false, false, false, false, false};
+    void mark(int k) {
+        hipEventRecord(ev[k], s);
+        on[k] = true;
+    }
+    // event k for a launcher that records it itself, if it will
+    hipEvent_t lend(int k, bool recorded) {
+        on[k] = recorded;
+        return ev[k];
+    }
+    float elapsed(int a, int b) const {
+        float t = 0;
+        if (on[a] && on[b]) hipEventElapsedTime(&t, ev[a], ev[b]);
+        return t;
+    }
+};
+
+// one total read back on the stream (the caller synchronises before it looks)
+template <class V>
+bool read_back(hipStream_t s, V* dst, const void* src) {
+    return hipMemcpyAsync(dst, src, sizeof(V), hipMemcpyDeviceToHost, s) == hipSuccess;
+}
+
+// where each family's phases start in lp_handle::tms (lp_last_timing index - 5)
+enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7 };
+
 }  // namespace
 
 struct lp_handle {
@@ -104,14 +159,11 @@ struct lp_handle {
     int64_t first_line = 0;        // global number of the last batch's first line
     int64_t next_line = 0;         // ... of the next batch's (lp_parse_batch continues the numbering)
     hipEvent_t ev[5]{};  // batch start, index done, parse start, batch end, parse kernels done
-    hipEvent_t tev[4]{}; // device table: start, values kernel done, scans done, bytes done
-    float tms[3] = {0, 0, 0};  // the last device table's values / scans / bytes phases
-    hipEvent_t mev[6]{}; // device map column: start / end of its count, entries and fill phases
-    float mms[3] = {0, 0, 0};  // the last device lp_result_table_map's phases, summed over its columns
-    hipEvent_t sev[2]{}; // device lp_result_select: start, end of its kernels
-    float sel_ms = 0;    // the last device lp_result_select's count pass, scan and write pass
-    hipEvent_t dev_ev[5]{};  // device lp_result_table_dict: a column's start, rows' values, insert, index, dictionary values
-    float dms[4] = {0, 0, 0, 0};  // the last device lp_result_table_dict's phases, summed over its columns
+    hipEvent_t tev[6]{}; // the device table calls' phase events (PhaseTimer): one pool, the calls are serialised
+    // lp_last_timing [5..15], each family's last successful device call: the table's values / scans /
+    // bytes phases; the map columns' count / entries / fill phases, summed over the columns;
+    // lp_result_select's passes and scan; the dictionary columns' four phases, summed over the columns
+    float tms[11]{};
     int dict_hash_bits = 0;  // LP_OPT_DICT_HASH_BITS (tests: 0 = the whole hash)
     bool have_events = false;
     uint64_t counters[4]{};
@@ -670,9 +722,6 @@ lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths,
     if (hipSetDevice(device) != hipSuccess) { if (status) *status = LP_E_DEVICE; return nullptr; }
     for (auto& ev : h->ev) hipEventCreate(&ev);
     for (auto& ev : h->tev) hipEventCreate(&ev);
-    for (auto& ev : h->mev) hipEventCreate(&ev);
-    for (auto& ev : h->sev) hipEventCreate(&ev);
-    for (auto& ev : h->dev_ev) hipEventCreate(&ev);
     h->have_events = true;
     if (!h->meta.ensure(sizeof(lp::Meta))) { if (status) *status = LP_E_NOMEM; return nullptr; }
     if (status) *status = st;
@@ -689,9 +738,6 @@ void lp_free(lp_handle* h) {
     if (h->have_events) {
         for (auto& ev : h->ev) hipEventDestroy(ev);
         for (auto& ev : h->tev) hipEventDestroy(ev);
-        for (auto& ev : h->mev) hipEventDestroy(ev);
-        for (auto& ev : h->sev) hipEventDestroy(ev);
-        for (auto& ev : h->dev_ev) hipEventDestroy(ev);
     }
     delete h;
 }
@@ -913,10 +959,7 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
     for (int k = 0; k < n && k < 5; ++k) out[k] = h->ms[k];
-    for (int k = 5; k < n && k < 8; ++k) out[k] = h->tms[k - 5];
-    for (int k = 8; k < n && k < 11; ++k) out[k] = h->mms[k - 8];
-    if (n > 11) out[11] = h->sel_ms;
-    for (int k = 12; k < n && k < 16; ++k) out[k] = h->dms[k - 12];
+    for (int k = 5; k < n && k < 16; ++k) out[k] = h->tms[k - 5];
     return n < 16 ? n : 16;
 }
 
@@ -1093,13 +1136,59 @@ static bool device_memory(lp_handle* h, const void* p) {
     return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == h->device;
 }
 
-// lp_result_table / lp_result_table_rows on a device view: the columns built
-// in HBM (table.hip).  rows (device memory, null: the lines first + k): row k
-// is line rows[k].
-static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_col* cols, int n_cols) {
-    if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines) || n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
-    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
+// ---- the checks and the plumbing the table families share.  Every family runs
+// them in this order: null arguments and the columns' own arrays; each path
+// (check_path); on a device view view_current, then check_rows and what only
+// the device refuses (LP_E_UNSUPPORTED); on a host copy the input, then check_rows.
+
+// A device view is only good for the batch the handle holds now
+static bool view_current(lp_handle* h, const lp_result* r) {
+    return !(!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
+             r->line_off != h->line_off.as<uint64_t>());
+}
+
+// Does the plan deliver path as a column of kind (LP_CAST_*)?  A pseudo-column
+// has no dissector and no casts entry: its kind is fixed.  Otherwise the casts
+// of the requested path (or of its wildcard request) must allow the kind: else
+// the reference's store finds no setter.  pseudo: the path's TC_* kind, 0 for none.
+static int check_path(lp_handle* h, const std::string& p, int kind, int* pseudo = nullptr) {
+    const int pk = lp::Plan::pseudo_kind(p);
+    if (pseudo) *pseudo = pk;
+    if (pk) return kind == (pk == lp::TC_LINE ? LP_CAST_STRING : LP_CAST_LONG) ? LP_OK : LP_E_INVALID;
+    int casts = h->plan.casts(p);
+    if (casts < 0) {
+        const size_t dot = p.rfind('.');
+        if (dot != std::string::npos) casts = h->plan.casts(p.substr(0, dot) + ".*");
+    }
+    return casts < 0 ? LP_E_MISSING : (casts & kind) ? LP_OK : LP_E_INVALID;
+}
+
+static bool check_window(int64_t first, int64_t count, const int64_t* rows, int64_t n_lines) {
+    return first >= 0 && count >= 0 && (rows || first + count <= n_lines);
+}
+
+// The window, or the row list, of a call on view r.  A host list: every index
+// inside the batch, before anything is written; a device list: memory of the
+// handle's device (the kernels dereference it and check the indices).
+static int check_rows(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows) {
+    const int64_t n_lines = r->on_host ? r->n_lines : h->n_lines;
+    if (!check_window(first, count, rows, n_lines)) return LP_E_INVALID;
+    if (!rows) return LP_OK;
+    if (!r->on_host) return count == 0 || device_memory(h, rows) ? LP_OK : LP_E_INVALID;
+    for (int64_t k = 0; k < count; ++k)
+        if (rows[k] < 0 || rows[k] >= n_lines) return LP_E_INVALID;
+    return LP_OK;
+}
+
+// The *_rows entry points' list: null only when it is empty (then the window [0, 0))
+static bool rows_arg(const int64_t*& rows, int64_t n_rows) {
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return false;
+    if (n_rows == 0) rows = nullptr;
+    return true;
+}
+
+// The table kernels' arguments of rows [first, first + count) / the row list
+static std::unique_ptr<lp::TableArgs> table_args(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, int n_cols) {
     auto ta = std::make_unique<lp::TableArgs>();
     memset(ta.get(), 0, sizeof(lp::TableArgs));
     ta->first = first;
@@ -1108,7 +1197,29 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_
     ta->rows = rows;
     ta->n_lines = h->n_lines;
     ta->first_line = h->first_line;
-    std::string names;
+    return ta;
+}
+
+// table.hip's scratch of a plain table, bound into ta: the scan's storage and
+// the value words, and 256 bytes after them the row-list instances' flag word
+static bool bind_table_scratch(lp_handle* h, lp::TableArgs& ta, int n_str) {
+    const size_t flag_at = align256(lp::table_scratch_bytes(ta.count, n_str));
+    if (!h->tscratch.ensure(flag_at + 256)) return false;
+    ta.srcw = reinterpret_cast<uint64_t*>((char*)h->tscratch.p + lp::table_srcw_offset(ta.count));
+    ta.bad_row = reinterpret_cast<uint32_t*>((char*)h->tscratch.p + flag_at);
+    return true;
+}
+
+// lp_result_table / lp_result_table_rows on a device view: the columns built
+// in HBM (table.hip).  rows (device memory, null: the lines first + k): row k
+// is line rows[k].
+static int table_device(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                        lp_table_col* cols, int n_cols) {
+    if (ensure_synced(h) != LP_OK) return LP_E_STATE;
+    if (n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
+    auto ta = table_args(h, first, count, rows, n_cols);
+    std::string names;  // (Plan::table_src keeps them within TableArgs::names)
     for (int c = 0; c < n_cols; ++c) {
         lp_table_col& C = cols[c];
         lp::TableCol& T = ta->cols[c];
@@ -1137,27 +1248,23 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_
     if (!h->targs.ensure(sizeof(lp::TableArgs))) return LP_E_NOMEM;
     int n_str = 0;
     for (int c = 0; c < n_cols; ++c) n_str += cols[c].kind == LP_CAST_STRING ? 1 : 0;
-    // (the row-list instances' flag word: 256 bytes after the value words)
-    const size_t scratch = lp::table_scratch_bytes(count, n_str), flag_at = (scratch + 255) & ~(size_t)255;
-    if (!h->tscratch.ensure(flag_at + 256)) return LP_E_NOMEM;
-    ta->srcw = reinterpret_cast<uint64_t*>((char*)h->tscratch.p + lp::table_srcw_offset(count));
-    ta->bad_row = reinterpret_cast<uint32_t*>((char*)h->tscratch.p + flag_at);
+    if (!bind_table_scratch(h, *ta, n_str)) return LP_E_NOMEM;
     const bool ext = lp::table_ext(*ta) && count > 0;
     if (hipMemcpyAsync(h->targs.p, ta.get(), sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess) return LP_E_DEVICE;
     const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
     const lp::TableArgs* d_targs = h->targs.as<lp::TableArgs>();
-    hipEventRecord(h->tev[0], s);
-    if (lp::launch_table_values(d_args, d_targs, *ta, h->d_buf, h->tscratch.p, h->tscratch.cap, s, h->tev[1]) != 0)
+    PhaseTimer T{h->tev, s};  // start, values kernel done, scans done, bytes done
+    T.mark(0);
+    // (an empty table launches nothing and records no event of its own)
+    if (lp::launch_table_values(d_args, d_targs, *ta, h->d_buf, h->tscratch.p, h->tscratch.cap, s, T.lend(1, count > 0)) != 0)
         return LP_E_DEVICE;
-    hipEventRecord(h->tev[2], s);
+    T.mark(2);
     // the STRING columns' byte counts decide whether their bytes fit
     std::vector<int64_t> tot(n_cols, 0);
     for (int c = 0; c < n_cols; ++c)
-        if (cols[c].kind == LP_CAST_STRING &&
-            hipMemcpyAsync(&tot[c], cols[c].i64 + count, 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return LP_E_DEVICE;
+        if (cols[c].kind == LP_CAST_STRING && !read_back(s, &tot[c], cols[c].i64 + count)) return LP_E_DEVICE;
     uint32_t bad_row = 0;  // a rows[k] outside the batch (its row: valid 0)
-    if (ext && hipMemcpyAsync(&bad_row, ta->bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+    if (ext && !read_back(s, &bad_row, ta->bad_row)) return LP_E_DEVICE;
     if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
     if (bad_row) return LP_E_INVALID;
     bool fits = true;
@@ -1168,20 +1275,10 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_
     }
     if (!fits) return LP_E_NOMEM;
     if (lp::launch_table_chars(d_args, d_targs, *ta, h->d_buf, s) != 0) return LP_E_DEVICE;
-    hipEventRecord(h->tev[3], s);
+    T.mark(3);
     if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
-    // An empty table records no tev[1]: asking for its time left hipErrorInvalidHandle
-    // behind, which the next launch's hipGetLastError took for its own (the next
-    // lp_parse_batch on the handle then failed with LP_E_DEVICE).  So an empty call keeps
-    // the previous call's lp_last_timing [5..7].
-    if (count == 0) return LP_OK;
-    float a = 0, b = 0, c = 0;
-    hipEventElapsedTime(&a, h->tev[0], h->tev[1]);
-    hipEventElapsedTime(&b, h->tev[1], h->tev[2]);
-    hipEventElapsedTime(&c, h->tev[2], h->tev[3]);
-    h->tms[0] = a;
-    h->tms[1] = b;
-    h->tms[2] = c;
+    if (count == 0) return LP_OK;  // (an empty call keeps the previous call's lp_last_timing [5..7])
+    for (int k = 0; k < 3; ++k) h->tms[TMS_TABLE + k] = T.elapsed(k, k + 1);
     return LP_OK;
 }
 
@@ -1190,64 +1287,25 @@ static int table_device(lp_handle* h, int64_t first, int64_t count, const int64_
 static int table_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
                      lp_table_col* cols, int n_cols, int threads) {
     if (!h || !r || !cols || n_cols <= 0) return LP_E_INVALID;
+    std::unordered_map<std::string, std::vector<int>> by_path;  // (a host copy's) path -> its columns
+    std::vector<int> pseudo(n_cols, 0);  // per column: its TC_* kind when it is a pseudo-column
     for (int c = 0; c < n_cols; ++c) {  // the same validation in both modes
         const lp_table_col& C = cols[c];
         if (!C.path || !C.valid || (C.kind == LP_CAST_STRING ? !C.i64 : C.kind == LP_CAST_LONG ? !C.i64 : !C.f64))
             return LP_E_INVALID;
         if (C.kind != LP_CAST_STRING && C.kind != LP_CAST_LONG && C.kind != LP_CAST_DOUBLE) return LP_E_INVALID;
-        std::string p = C.path;
-        if (const int pk = lp::Plan::pseudo_kind(p)) {  // a pseudo-column: no dissector, no casts entry
-            if (C.kind != (pk == lp::TC_LINE ? LP_CAST_STRING : LP_CAST_LONG)) return LP_E_INVALID;
-            continue;
-        }
-        int casts = h->plan.casts(p);
-        if (casts < 0) {
-            const size_t dot = p.rfind('.');
-            if (dot != std::string::npos) casts = h->plan.casts(p.substr(0, dot) + ".*");
-        }
-        if (casts < 0) return LP_E_MISSING;
-        if (!(casts & C.kind)) return LP_E_INVALID;
+        if (const int st = check_path(h, C.path, C.kind, &pseudo[c])) return st;
+        if (r->on_host && !pseudo[c]) by_path[C.path].push_back(c);
     }
-    if (!r->on_host) {
-        // a device view is only good for the batch the handle holds now
-        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
-            r->line_off != h->line_off.as<uint64_t>())
-            return LP_E_STATE;
-        return table_device(h, first, count, rows, cols, n_cols);
-    }
+    if (!r->on_host) return view_current(h, r) ? table_device(h, r, first, count, rows, cols, n_cols) : LP_E_STATE;
     if (!r->input) return LP_E_INVALID;
-    if (first < 0 || count < 0 || (!rows && first + count > r->n_lines)) return LP_E_INVALID;
-    if (rows)  // every index inside the batch, before anything is written
-        for (int64_t k = 0; k < count; ++k)
-            if (rows[k] < 0 || rows[k] >= r->n_lines) return LP_E_INVALID;
-    std::unordered_map<std::string, std::vector<int>> by_path;
-    std::vector<int> pseudo(n_cols, 0);  // per column: its TC_* kind when it is a pseudo-column
-    for (int c = 0; c < n_cols; ++c) {
-        const lp_table_col& C = cols[c];
-        if (!C.path || !C.valid || (C.kind == LP_CAST_STRING ? !C.i64 : C.kind == LP_CAST_LONG ? !C.i64 : !C.f64))
-            return LP_E_INVALID;
-        if (C.kind != LP_CAST_STRING && C.kind != LP_CAST_LONG && C.kind != LP_CAST_DOUBLE) return LP_E_INVALID;
-        // the casts of the requested path (or of its wildcard request) must
-        // allow the column type: else the reference's store finds no setter
-        std::string p = C.path;
-        if ((pseudo[c] = lp::Plan::pseudo_kind(p))) continue;  // (its kind was checked above)
-        int casts = h->plan.casts(p);
-        if (casts < 0) {
-            const size_t dot = p.rfind('.');
-            if (dot != std::string::npos) casts = h->plan.casts(p.substr(0, dot) + ".*");
-        }
-        if (casts < 0) return LP_E_MISSING;
-        if (!(casts & C.kind)) return LP_E_INVALID;
-        by_path[p].push_back(c);
-    }
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
     lp::ResultView V;
     make_view(h, *r, V);
-    const int T = std::max(1, std::min(threads > 0 ? threads : 1, 64));
-    const int64_t per = (count + T - 1) / T;
-    std::vector<std::vector<std::string>> sbuf(T, std::vector<std::string>(n_cols));
-    std::vector<std::vector<std::vector<std::pair<uint64_t, uint32_t>>>> sref(T);
-    auto work = [&](int t) {
-        const int64_t a = std::min(count, t * per), b = std::min(count, a + per);
+    const Chunks ch(count, threads);
+    std::vector<std::vector<std::string>> sbuf(ch.T, std::vector<std::string>(n_cols));
+    std::vector<std::vector<std::vector<std::pair<uint64_t, uint32_t>>>> sref(ch.T);
+    ch.run([&](int t, int64_t a, int64_t b) {
         sref[t].assign(n_cols, std::vector<std::pair<uint64_t, uint32_t>>((size_t)(b - a), {0ull, 0u}));
         TableCtx ctx{&by_path, cols, 0, &sbuf[t], &sref[t], a};
         for (int64_t k = a; k < b; ++k) {
@@ -1275,11 +1333,7 @@ static int table_any(lp_handle* h, const lp_result* r, int64_t first, int64_t co
             ctx.row = k;
             h->plan.rec_row(V, i, table_value, &ctx);
         }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
+    });
     // STRING columns (Arrow layout): row k = chars[offsets[k], offsets[k + 1]),
     // the row's last value; a row without one is empty (valid 0)
     int rc = LP_OK;
@@ -1287,19 +1341,20 @@ static int table_any(lp_handle* h, const lp_result* r, int64_t first, int64_t co
         lp_table_col& C = cols[c];
         if (C.kind != LP_CAST_STRING) continue;
         uint64_t need = 0;
-        for (int64_t k = 0; k < count; ++k)
-            if (C.valid[k]) need += sref[(size_t)(k / per)][c][(size_t)(k % per)].second;
+        for (int t = 0; t < ch.T; ++t)
+            for (int64_t k = ch.at[t]; k < ch.at[t + 1]; ++k)
+                if (C.valid[k]) need += sref[t][c][(size_t)(k - ch.at[t])].second;
         C.chars_len = need;
         if (need > C.chars_cap || (need && !C.chars)) { rc = LP_E_NOMEM; continue; }
         uint64_t pos = 0;
-        for (int64_t k = 0; k < count; ++k) {
-            C.i64[k] = (int64_t)pos;
-            if (!C.valid[k]) continue;
-            const int t = (int)(k / per);
-            const auto& pr = sref[(size_t)t][c][(size_t)(k % per)];
-            memcpy(C.chars + pos, sbuf[(size_t)t][c].data() + pr.first, pr.second);
-            pos += pr.second;
-        }
+        for (int t = 0; t < ch.T; ++t)
+            for (int64_t k = ch.at[t]; k < ch.at[t + 1]; ++k) {
+                C.i64[k] = (int64_t)pos;
+                if (!C.valid[k]) continue;
+                const auto& pr = sref[t][c][(size_t)(k - ch.at[t])];
+                memcpy(C.chars + pos, sbuf[t][c].data() + pr.first, pr.second);
+                pos += pr.second;
+            }
         C.i64[count] = (int64_t)pos;
     }
     return rc;
@@ -1312,8 +1367,7 @@ int lp_result_table(lp_handle* h, const lp_result* r, int64_t first, int64_t cou
 
 int lp_result_table_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows, lp_table_col* cols,
                          int n_cols, int threads) {
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
-    return table_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
+    return rows_arg(rows, n_rows) ? table_any(h, r, 0, n_rows, rows, cols, n_cols, threads) : LP_E_INVALID;
 }
 
 // ---- dictionary-encoded STRING columns (Arrow dictionary<int32, utf8>)
@@ -1324,11 +1378,11 @@ int lp_result_table_rows(lp_handle* h, const lp_result* r, const int64_t* rows, 
 // offsets), the hash insert, the representatives' ranks and the indices, then
 // the dictionary's values as the STRING column of the representatives' lines
 // by the table's row-list instances.
-static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_dict_col* cols,
-                             int n_cols) {
+static int table_dict_device(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                             lp_table_dict_col* cols, int n_cols) {
     if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines) || n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
-    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
+    if (n_cols > lp::MAX_TABLE_COLS) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
     for (int c = 0; c < n_cols; ++c) {  // every array the kernels write is memory of the device
         const lp_table_dict_col& C = cols[c];
         if (!device_memory(h, C.dict_off) || (count > 0 && (!device_memory(h, C.valid) || !device_memory(h, C.index))) ||
@@ -1338,19 +1392,11 @@ static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const i
     // every column's sources before anything is written
     std::vector<std::unique_ptr<lp::TableArgs>> tas;
     for (int c = 0; c < n_cols; ++c) {
-        auto ta = std::make_unique<lp::TableArgs>();
-        memset(ta.get(), 0, sizeof(lp::TableArgs));
-        ta->first = first;
-        ta->count = count;
-        ta->n_cols = 1;
-        ta->rows = rows;
-        ta->n_lines = h->n_lines;
-        ta->first_line = h->first_line;
-        std::string names;
+        auto ta = table_args(h, first, count, rows, 1);
+        std::string names;  // (Plan::table_src keeps them within TableArgs::names)
         lp::TableCol& T = ta->cols[0];
         T.kind = LP_CAST_STRING;
         if (!h->plan.table_src(cols[c].path, T.src, names, T.alt)) return LP_E_UNSUPPORTED;
-        if (names.size() > sizeof(ta->names)) return LP_E_UNSUPPORTED;
         memcpy(ta->names, names.data(), names.size());
         T.valid = cols[c].valid;
         tas.push_back(std::move(ta));
@@ -1382,19 +1428,18 @@ static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const i
         lp::dict_bind(da, ta, L, scratch);
         const bool ext = lp::table_ext(ta);
         if (hipMemcpyAsync(h->targs.p, &ta, sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess) return LP_E_DEVICE;
-        hipEventRecord(h->dev_ev[0], s);
+        PhaseTimer T{h->tev, s};  // the column's start, rows' values, insert, index, dictionary values
+        T.mark(0);
         if (lp::launch_table_values(d_args, d_targs, ta, h->d_buf, scratch, L.table_bytes, s, nullptr, false) != 0)
             return LP_E_DEVICE;
-        hipEventRecord(h->dev_ev[1], s);
+        T.mark(1);
         if (lp::launch_dict_insert(d_args, d_targs, ta, da, h->d_buf, s) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->dev_ev[2], s);
+        T.mark(2);
         const uint32_t* d_total = nullptr;
         if (lp::launch_dict_rank(da, L, scratch, s, &d_total) != 0 || lp::launch_dict_index(ta, da, s) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->dev_ev[3], s);
+        T.mark(3);
         uint32_t total = 0, fail = 0, bad_row = 0;
-        if (hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(&fail, da.fail, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (ext && hipMemcpyAsync(&bad_row, ta.bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess))
+        if (!read_back(s, &total, d_total) || !read_back(s, &fail, da.fail) || (ext && !read_back(s, &bad_row, ta.bad_row)))
             return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         if (bad_row) return LP_E_INVALID;  // a rows[k] outside the batch
@@ -1417,8 +1462,7 @@ static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const i
             if (hipMemcpyAsync(h->targs.p, &tv, sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess)
                 return LP_E_DEVICE;
             if (lp::launch_table_values(d_args, d_targs, tv, h->d_buf, scratch, L.table_bytes, s) != 0) return LP_E_DEVICE;
-            if (hipMemcpyAsync(&bytes, tv.cols[0].i64 + C.dict_len, 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-                return LP_E_DEVICE;
+            if (!read_back(s, &bytes, tv.cols[0].i64 + C.dict_len)) return LP_E_DEVICE;
         }
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         C.dict_chars_len = (uint64_t)bytes;
@@ -1427,16 +1471,12 @@ static int table_dict_device(lp_handle* h, int64_t first, int64_t count, const i
             continue;
         }
         if (C.dict_len > 0 && lp::launch_table_chars(d_args, d_targs, tv, h->d_buf, s) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->dev_ev[4], s);
+        T.mark(4);
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
-        for (int k = 0; k < 4; ++k) {
-            float t = 0;
-            hipEventElapsedTime(&t, h->dev_ev[k], h->dev_ev[k + 1]);
-            ms[k] += t;
-        }
+        for (int k = 0; k < 4; ++k) ms[k] += T.elapsed(k, k + 1);
     }
     if (rc == LP_OK)
-        for (int k = 0; k < 4; ++k) h->dms[k] = ms[k];
+        for (int k = 0; k < 4; ++k) h->tms[TMS_DICT + k] = ms[k];
     return rc;
 }
 
@@ -1448,42 +1488,23 @@ static int table_dict_any(lp_handle* h, const lp_result* r, int64_t first, int64
         const lp_table_dict_col& C = cols[c];
         if (!C.path || !C.dict_off || C.dict_cap < 0 || (count > 0 && (!C.valid || !C.index))) return LP_E_INVALID;
     }
-    // the plain STRING column of the path: its checks are this call's
+    for (int c = 0; c < n_cols; ++c)  // the plain STRING column of the path: its checks are this call's
+        if (const int st = check_path(h, cols[c].path, LP_CAST_STRING)) return st;
+    if (!r->on_host) return view_current(h, r) ? table_dict_device(h, r, first, count, rows, cols, n_cols) : LP_E_STATE;
+    if (!r->input) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
+    // a host copy: the host table's plain column, then a hash map in row order
     std::vector<lp_table_col> tc((size_t)n_cols);
-    int64_t dummy_off[2] = {0, 0};
-    uint8_t dummy_valid = 0;
+    std::vector<std::vector<int64_t>> off((size_t)n_cols, std::vector<int64_t>((size_t)count + 1, 0));
+    std::vector<std::vector<char>> chars((size_t)n_cols);
+    uint8_t dummy_valid = 0;  // (an empty table's valid may be null)
     for (int c = 0; c < n_cols; ++c) {
         tc[c] = lp_table_col{};
         tc[c].path = cols[c].path;
         tc[c].kind = LP_CAST_STRING;
         tc[c].valid = cols[c].valid ? cols[c].valid : &dummy_valid;
-        tc[c].i64 = dummy_off;
+        tc[c].i64 = off[c].data();
     }
-    if (!r->on_host) {
-        // table_any's checks of a STRING column's path, and of the view
-        for (int c = 0; c < n_cols; ++c) {
-            std::string p = cols[c].path;
-            if (const int pk = lp::Plan::pseudo_kind(p)) {
-                if (pk != lp::TC_LINE) return LP_E_INVALID;
-                continue;
-            }
-            int casts = h->plan.casts(p);
-            if (casts < 0) {
-                const size_t dot = p.rfind('.');
-                if (dot != std::string::npos) casts = h->plan.casts(p.substr(0, dot) + ".*");
-            }
-            if (casts < 0) return LP_E_MISSING;
-            if (!(casts & LP_CAST_STRING)) return LP_E_INVALID;
-        }
-        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
-            r->line_off != h->line_off.as<uint64_t>())
-            return LP_E_STATE;
-        return table_dict_device(h, first, count, rows, cols, n_cols);
-    }
-    // a host copy: the host table's plain column, then a hash map in row order
-    std::vector<std::vector<int64_t>> off((size_t)n_cols, std::vector<int64_t>((size_t)count + 1, 0));
-    std::vector<std::vector<char>> chars((size_t)n_cols);
-    for (int c = 0; c < n_cols; ++c) tc[c].i64 = off[c].data();
     int st = table_any(h, r, first, count, rows, tc.data(), n_cols, threads);
     if (st == LP_E_NOMEM) {
         for (int c = 0; c < n_cols; ++c) {
@@ -1540,8 +1561,7 @@ int lp_result_table_dict(lp_handle* h, const lp_result* r, int64_t first, int64_
 
 int lp_result_table_dict_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows,
                               lp_table_dict_col* cols, int n_cols, int threads) {
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
-    return table_dict_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
+    return rows_arg(rows, n_rows) ? table_dict_any(h, r, 0, n_rows, rows, cols, n_cols, threads) : LP_E_INVALID;
 }
 
 // ---- wildcard targets as map columns (ParsedRecord.setMultiValueString)
@@ -1580,11 +1600,10 @@ void map_member(void* vctx, const std::string& wildcard, const std::string& key,
 
 // lp_result_table_map / lp_result_table_map_rows on a device view: the columns
 // built in HBM (table.hip).  rows as table_device's.
-static int table_map_device(lp_handle* h, int64_t first, int64_t count, const int64_t* rows, lp_table_map_col* cols,
-                            int n_cols) {
+static int table_map_device(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                            lp_table_map_col* cols, int n_cols) {
     if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-    if (first < 0 || count < 0 || (!rows && first + count > h->n_lines)) return LP_E_INVALID;
-    if (rows && count > 0 && !device_memory(h, rows)) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
     std::vector<lp::MapArgs> args((size_t)n_cols);
     for (int c = 0; c < n_cols; ++c) {
         lp::MapArgs& M = args[(size_t)c];
@@ -1614,17 +1633,16 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, const in
         if (!h->tscratch.ensure(lp::map_scratch_bytes(count, 0))) return LP_E_NOMEM;
         const int64_t* d_total = nullptr;
         int64_t pieces = 0;
-        hipEventRecord(h->mev[0], s);
+        PhaseTimer T{h->tev, s};  // start / end of the column's count, entries and fill phases
+        T.mark(0);
         if (lp::launch_map_count(d_args, M, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->mev[1], s);
-        if (hipMemcpyAsync(&pieces, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        T.mark(1);
+        if (!read_back(s, &pieces, d_total)) return LP_E_DEVICE;
         uint32_t bad_row = 0;  // a rows[k] outside the batch (its row: valid 0, no entries)
-        if (rows && hipMemcpyAsync(&bad_row, M.bad_row, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        if (rows && !read_back(s, &bad_row, M.bad_row)) return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         if (bad_row) return LP_E_INVALID;
-        float t = 0;
-        hipEventElapsedTime(&t, h->mev[0], h->mev[1]);
-        ms[0] += t;
+        ms[0] += T.elapsed(0, 1);
         if (pieces >= 0x7FFFFFFF) return LP_E_UNSUPPORTED;  // (the scans count in ints: build it in windows)
         if (pieces == 0) {  // no entries: every row's map is empty
             if (hipMemsetAsync(C.entry_off, 0, 8 * ((size_t)count + 1), s) != hipSuccess ||
@@ -1642,16 +1660,13 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, const in
         const void* d_tot[3] = {nullptr, nullptr, nullptr};
         uint32_t entries = 0;
         int64_t kbytes = 0, vbytes = 0;
-        hipEventRecord(h->mev[2], s);
+        T.mark(2);
         if (lp::launch_map_entries(d_args, M, h->d_buf, h->tscratch.p, h->tscratch.cap, s, d_tot) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->mev[3], s);
-        if (hipMemcpyAsync(&entries, d_tot[0], 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(&kbytes, d_tot[1], 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(&vbytes, d_tot[2], 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+        T.mark(3);
+        if (!read_back(s, &entries, d_tot[0]) || !read_back(s, &kbytes, d_tot[1]) || !read_back(s, &vbytes, d_tot[2]))
             return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
-        hipEventElapsedTime(&t, h->mev[2], h->mev[3]);
-        ms[1] += t;
+        ms[1] += T.elapsed(2, 3);
         C.entries_len = entries;
         C.key_chars_len = (uint64_t)kbytes;
         C.val_chars_len = (uint64_t)vbytes;
@@ -1659,16 +1674,15 @@ static int table_map_device(lp_handle* h, int64_t first, int64_t count, const in
             (kbytes && !C.key_chars) || (vbytes && !C.val_chars))
             rc = LP_E_NOMEM;
         if (rc != LP_OK) continue;  // (the later columns' lengths still)
-        hipEventRecord(h->mev[4], s);
+        T.mark(4);
         if (lp::launch_map_fill(M, (int64_t)entries, h->tscratch.p, h->tscratch.cap, s) != 0) return LP_E_DEVICE;
-        hipEventRecord(h->mev[5], s);
+        T.mark(5);
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
-        hipEventElapsedTime(&t, h->mev[4], h->mev[5]);
-        ms[2] += t;
+        ms[2] += T.elapsed(4, 5);
     }
     if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
     if (rc == LP_OK)
-        for (int k = 0; k < 3; ++k) h->mms[k] = ms[k];
+        for (int k = 0; k < 3; ++k) h->tms[TMS_MAP + k] = ms[k];
     return rc;
 }
 
@@ -1683,30 +1697,18 @@ static int table_map_any(lp_handle* h, const lp_result* r, int64_t first, int64_
         if (!C.path || !C.valid || !C.entry_off || !C.key_off || !C.val_off) return LP_E_INVALID;
         const std::string p = C.path;
         if (p.size() < 2 || p.compare(p.size() - 2, 2, ".*") != 0) return LP_E_INVALID;  // not a wildcard
-        const int casts = h->plan.casts(p);
-        if (casts < 0) return LP_E_MISSING;
-        if (!(casts & LP_CAST_STRING)) return LP_E_INVALID;
+        if (const int st = check_path(h, p, LP_CAST_STRING)) return st;  // (its wildcard request is the path itself)
         by_path[p].push_back(c);
     }
-    if (!r->on_host) {
-        // a device view is only good for the batch the handle holds now
-        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
-            r->line_off != h->line_off.as<uint64_t>())
-            return LP_E_STATE;
-        return table_map_device(h, first, count, rows, cols, n_cols);
-    }
+    if (!r->on_host) return view_current(h, r) ? table_map_device(h, r, first, count, rows, cols, n_cols) : LP_E_STATE;
     if (!r->input) return LP_E_INVALID;
-    if (first < 0 || count < 0 || (!rows && first + count > r->n_lines)) return LP_E_INVALID;
-    if (rows)  // every index inside the batch, before anything is written
-        for (int64_t k = 0; k < count; ++k)
-            if (rows[k] < 0 || rows[k] >= r->n_lines) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
     lp::ResultView V;
     make_view(h, *r, V);
-    const int T = std::max(1, std::min(threads > 0 ? threads : 1, 64));
-    const int64_t per = (count + T - 1) / T;
+    const Chunks ch(count, threads);
+    const int T = ch.T;
     std::vector<std::vector<MapChunk>> chunk(T, std::vector<MapChunk>(n_cols));
-    auto work = [&](int t) {
-        const int64_t a = std::min(count, t * per), b = std::min(count, a + per);
+    ch.run([&](int t, int64_t a, int64_t b) {
         std::vector<std::vector<MapRowCtx::Item>> items(n_cols);
         std::vector<std::unordered_map<std::string, size_t>> last(n_cols);
         MapRowCtx ctx{&by_path, &items, &last};
@@ -1733,11 +1735,7 @@ static int table_map_any(lp_handle* h, const lp_result* r, int64_t first, int64_
                 }
             }
         }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
+    });
     // Arrow MapArray: row k = entries [entry_off[k], entry_off[k + 1]); entry e =
     // key_chars[key_off[e], key_off[e + 1]) -> val_chars[val_off[e], val_off[e + 1])
     int rc = LP_OK;
@@ -1791,8 +1789,7 @@ int lp_result_table_map(lp_handle* h, const lp_result* r, int64_t first, int64_t
 
 int lp_result_table_map_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows, lp_table_map_col* cols,
                              int n_cols, int threads) {
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return LP_E_INVALID;
-    return table_map_any(h, r, 0, n_rows, n_rows ? rows : nullptr, cols, n_cols, threads);
+    return rows_arg(rows, n_rows) ? table_map_any(h, r, 0, n_rows, rows, cols, n_cols, threads) : LP_E_INVALID;
 }
 
 // The lines of a window whose status is in status_mask, ascending (select.hip on
@@ -1803,12 +1800,8 @@ int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t co
     if (status_mask & ~(uint32_t)(LP_SEL_OK | LP_SEL_BAD | LP_SEL_FALLBACK)) return LP_E_INVALID;
     *rows_len = 0;
     if (!r->on_host) {
-        // a device view is only good for the batch the handle holds now
-        if (!h->valid || r->n_lines != h->n_lines || r->first_line != h->first_line || r->input != h->d_buf ||
-            r->line_off != h->line_off.as<uint64_t>())
-            return LP_E_STATE;
-        if (ensure_synced(h) != LP_OK) return LP_E_STATE;
-        if (first < 0 || count < 0 || first + count > h->n_lines) return LP_E_INVALID;
+        if (!view_current(h, r) || ensure_synced(h) != LP_OK) return LP_E_STATE;
+        if (!check_window(first, count, nullptr, h->n_lines)) return LP_E_INVALID;
         if (rows_cap && !device_memory(h, rows)) return LP_E_INVALID;
         if (count == 0 || status_mask == 0) return LP_OK;
         hipSetDevice(h->device);
@@ -1816,24 +1809,25 @@ int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t co
         if (!h->tscratch.ensure(lp::select_scratch_bytes(first, count))) return LP_E_NOMEM;
         const int64_t* d_total = nullptr;
         int64_t total = 0;
-        hipEventRecord(h->sev[0], s);
+        PhaseTimer T{h->tev, s};  // start, end of its kernels
+        T.mark(0);
         if (lp::launch_select_count(h->C.status, first, count, status_mask, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0)
             return LP_E_DEVICE;
         // the number of selected lines decides whether they fit
-        if (hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return LP_E_DEVICE;
+        if (!read_back(s, &total, d_total)) return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         *rows_len = (uint64_t)total;
         if ((uint64_t)total > rows_cap) return LP_E_NOMEM;
         if (total > 0 &&
             lp::launch_select_write(h->C.status, first, count, status_mask, rows, h->tscratch.p, h->tscratch.cap, s) != 0)
             return LP_E_DEVICE;
-        hipEventRecord(h->sev[1], s);
+        T.mark(1);
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         // (the host's read of the total between the passes is inside the interval)
-        hipEventElapsedTime(&h->sel_ms, h->sev[0], h->sev[1]);
+        h->tms[TMS_SELECT] = T.elapsed(0, 1);
         return LP_OK;
     }
-    if (first < 0 || count < 0 || first + count > r->n_lines) return LP_E_INVALID;
+    if (!check_window(first, count, nullptr, r->n_lines)) return LP_E_INVALID;
     lp::ResultView V;
     make_view(h, *r, V);
     if (!V.status && count > 0) return LP_E_INVALID;
