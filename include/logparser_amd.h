@@ -217,8 +217,11 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * view, summed over its columns: [12] k_table_values of the rows, [13] the
  * table reset and k_dict_insert, [14] k_dict_mark, the rank scan and
  * k_dict_index, [15] the dictionary's values (k_table_values, the offset scan
- * and k_table_chars over the representatives).  Returns the number of values
- * written (at most 16). */
+ * and k_table_chars over the representatives); then [16] the last complete
+ * lp_result_arrow on a device view: its packaging kernels (k_arrow_validity's
+ * bitmaps and counts, k_arrow_narrow32), summed over the columns.  [16] is
+ * written only for n >= 17: a caller that passes 16 sees what it always saw.
+ * Returns the number of values written (at most 17). */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -559,6 +562,155 @@ int lp_result_table_dict(lp_handle *h, const lp_result *r, int64_t first, int64_
                          int n_cols, int threads);
 int lp_result_table_dict_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
                               lp_table_dict_col *cols, int n_cols, int threads);
+
+/* ---- Arrow C Data Interface export of the typed, dictionary and map columns. ----
+ * One call turns rows of a batch into an Arrow record batch that any Arrow
+ * consumer imports as it is (Arrow Java's Data.importVectorSchemaRoot,
+ * pyarrow's RecordBatch._import_from_c, the ORC / Parquet writers): the
+ * columns the Hadoop ParsedRecord holds per line and the Hive SerDe reads
+ * back (httpdlog-inputformat/.../ParsedRecord.java:154-214,
+ * httpdlog-serde/.../ApacheHttpdlogDeserializer.java:224-240, 295-323) and
+ * the ".*" map the record reader registers and the Pig Loader returns
+ * (ApacheHttpdLogfileRecordReader.java:206-208, httpdlog-pigloader/.../
+ * Loader.java:227-229), with what Arrow wants and the table calls above do
+ * not give: validity BITMAPS with exact null counts, int32 map offsets, the
+ * nested struct / map / dictionary tree, and a lifetime of their own.
+ *
+ * The three structures are the Arrow specification's, under its guards: a
+ * consumer that also includes Arrow's abi.h sees no redefinition. */
+#ifndef ARROW_C_DATA_INTERFACE
+#define ARROW_C_DATA_INTERFACE
+#define ARROW_FLAG_DICTIONARY_ORDERED 1
+#define ARROW_FLAG_NULLABLE 2
+#define ARROW_FLAG_MAP_KEYS_SORTED 4
+struct ArrowSchema {
+    const char *format;
+    const char *name;
+    const char *metadata;
+    int64_t flags;
+    int64_t n_children;
+    struct ArrowSchema **children;
+    struct ArrowSchema *dictionary;
+    void (*release)(struct ArrowSchema *);
+    void *private_data;
+};
+struct ArrowArray {
+    int64_t length;
+    int64_t null_count;
+    int64_t offset;
+    int64_t n_buffers;
+    int64_t n_children;
+    const void **buffers;
+    struct ArrowArray **children;
+    struct ArrowArray *dictionary;
+    void (*release)(struct ArrowArray *);
+    void *private_data;
+};
+#endif
+#ifndef ARROW_C_DEVICE_DATA_INTERFACE
+#define ARROW_C_DEVICE_DATA_INTERFACE
+typedef int32_t ArrowDeviceType;
+#define ARROW_DEVICE_CPU 1
+#define ARROW_DEVICE_ROCM 10
+struct ArrowDeviceArray {
+    struct ArrowArray array;
+    int64_t device_id;
+    ArrowDeviceType device_type;
+    void *sync_event;
+    int64_t reserved[3];
+};
+#endif
+
+/* A column of lp_result_arrow.  The layout (offset 0 everywhere; the top level
+ * a non-nullable struct "+s" of `length` rows, one child per column in the
+ * order given):
+ *   PLAIN LONG    "l"  validity, the i64 values                       nullable
+ *   PLAIN DOUBLE  "g"  validity, the f64 values                       nullable
+ *   PLAIN STRING  "U"  (large_utf8) validity, the int64 offsets as the table
+ *                      writes them (no narrowing, no copy), chars     nullable
+ *   "@line"       "Z"  (large_binary: its bytes are not validated UTF-8)
+ *   DICT          "i"  validity, index; nullable; dictionary = a non-nullable
+ *                      "U" array of dict_len entries (dict_off, dict_chars);
+ *                      ARROW_FLAG_DICTIONARY_ORDERED not set
+ *   MAP           "+m" validity, int32 offsets [rows + 1] NARROWED from
+ *                      entry_off; nullable; ARROW_FLAG_MAP_KEYS_SORTED not set;
+ *                      one child "entries" ("+s", not nullable, entries_len
+ *                      long) of "key" ("U", not nullable: key_off / key_chars)
+ *                      and "value" ("U", nullable, null_count 0, no bitmap:
+ *                      val_off / val_chars)
+ * Validity is Arrow's bitmap: bit k & 7 of byte k >> 3 is set when the table's
+ * valid[k] != 0, every bit at or past `length` is 0, the allocation a multiple
+ * of 64 bytes; null_count is always exact (never -1); a column without nulls
+ * has a NULL validity pointer and no bitmap (the dense table of the OK lines
+ * costs nothing). */
+#define LP_ARROW_PLAIN 0   /* kind = LP_CAST_STRING / LP_CAST_LONG / LP_CAST_DOUBLE */
+#define LP_ARROW_DICT  1   /* lp_result_table_dict's column */
+#define LP_ARROW_MAP   2   /* lp_result_table_map's column (a ".*" path) */
+typedef struct lp_arrow_col {
+    const char *path;      /* as the table calls take it, pseudo-columns included */
+    const char *name;      /* Arrow field name; NULL: the path */
+    int32_t form;          /* LP_ARROW_* */
+    int32_t kind;          /* LP_ARROW_PLAIN only */
+} lp_arrow_col;
+
+/* The rows of a batch as an Arrow record batch.  rows == NULL: the window
+ * [first, first+count); else row k = line rows[k] (n_rows in count, first
+ * ignored), exactly as the *_rows calls.  From a host copy array_out->array is
+ * an importable ArrowArray in malloc'ed memory (device_type ARROW_DEVICE_CPU,
+ * device_id -1); on a device view every buffer is hipMalloc'ed memory of the
+ * handle's device (ARROW_DEVICE_ROCM, device_id the handle's device) and the
+ * bitmaps, null counts and int32 offsets are made by kernels.  sync_event is
+ * NULL: the call returns after its stream is synchronised, as the table calls
+ * do, so the buffers are complete when it returns.
+ * The call allocates every buffer itself and runs the tables' LP_E_NOMEM size
+ * protocol inside; the batch belongs to the consumer until it calls the
+ * release callbacks and OUTLIVES the handle's next batch and the handle.
+ * Errors: n_cols == 0, an unknown form, or a map with more than 2^31 - 1
+ * entries (build it in windows) is LP_E_INVALID; every other code is the
+ * underlying table call's, unchanged (LP_E_MISSING, LP_E_UNSUPPORTED,
+ * LP_E_INVALID, LP_E_STATE, a row index outside the batch).  On any error both
+ * outputs are released (release == NULL) and nothing leaks.  count == 0 gives
+ * valid zero-length arrays whose offsets buffers hold the single 0.
+ * lp_last_timing [16]: the last device export's packaging kernels. */
+int lp_result_arrow(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t first, int64_t count,
+                    const lp_arrow_col *cols, int n_cols, int threads, struct ArrowSchema *schema_out,
+                    struct ArrowDeviceArray *array_out);
+
+/* The packaging alone, without a handle: wrap columns that table calls (or
+ * anything else) already filled, n_rows rows each.  device < 0: host memory;
+ * else memory of that device, and stream (a hipStream_t, NULL = the default
+ * stream) carries the kernels; the call returns after synchronising it.
+ * Children: the plain columns, then the dictionary columns, then the maps.
+ * A column's Arrow field name is *_names[i], or its path when the names array
+ * or the entry is NULL.  Of a column only its arrays, kind and lengths
+ * (chars_len, dict_len, entries_len, ...) are read; valid may have any
+ * alignment.
+ * It WRAPS: no value buffer is copied.  It allocates the bitmaps, the narrowed
+ * map offsets and the structures, and frees exactly those on release.
+ * owner->free_fn(owner->ctx) is called exactly once, when the last exported
+ * ARRAY structure has been released (the record batch, any child or
+ * dictionary the consumer moved out of it); the schema holds no buffer and
+ * releases independently, in either order.  owner may be NULL.  When the call
+ * fails the owner is NOT called: the buffers stay the caller's.
+ * The release callbacks follow the specification: a child the consumer moved
+ * out (its release NULL) is skipped, release is set to NULL last, and
+ * private_data is ours. */
+typedef struct lp_arrow_owner {
+    void (*free_fn)(void *ctx);
+    void *ctx;
+} lp_arrow_owner;
+int lp_arrow_from_tables(int device, void *stream, int64_t n_rows,
+                         const lp_table_col *plain, const char *const *plain_names, int n_plain,
+                         const lp_table_dict_col *dict, const char *const *dict_names, int n_dict,
+                         const lp_table_map_col *map, const char *const *map_names, int n_map,
+                         const lp_arrow_owner *owner, struct ArrowSchema *schema_out,
+                         struct ArrowDeviceArray *array_out);
+
+/* Deep copy of a record batch of the types above to host memory, for a
+ * consumer whose Arrow build has no ROCm memory manager (pyarrow among them).
+ * `in` stays the caller's to release; `out` is an independent ArrowArray of
+ * malloc'ed buffers.  LP_E_INVALID for a format this library does not export. */
+int lp_arrow_to_host(const struct ArrowSchema *schema, const struct ArrowDeviceArray *in, struct ArrowArray *out);
 
 /* Description of the compiled device program (for logs/tests), NUL-terminated. */
 int64_t lp_describe(lp_handle *h, char *out, size_t cap);

@@ -78,6 +78,57 @@ class LpTableDictCol(ctypes.Structure):
                 ("dict_chars_cap", ctypes.c_uint64), ("dict_len", ctypes.c_int64), ("dict_chars_len", ctypes.c_uint64)]
 
 
+class ArrowSchema(ctypes.Structure):
+    """struct ArrowSchema of the Arrow C Data Interface (include/logparser_amd.h)"""
+
+
+ArrowSchema._fields_ = [("format", ctypes.c_char_p), ("name", ctypes.c_char_p), ("metadata", ctypes.c_void_p),
+                        ("flags", ctypes.c_int64), ("n_children", ctypes.c_int64),
+                        ("children", ctypes.POINTER(ctypes.POINTER(ArrowSchema))),
+                        ("dictionary", ctypes.POINTER(ArrowSchema)),
+                        ("release", ctypes.CFUNCTYPE(None, ctypes.POINTER(ArrowSchema))),
+                        ("private_data", ctypes.c_void_p)]
+
+
+class ArrowArray(ctypes.Structure):
+    """struct ArrowArray of the Arrow C Data Interface"""
+
+
+ArrowArray._fields_ = [("length", ctypes.c_int64), ("null_count", ctypes.c_int64), ("offset", ctypes.c_int64),
+                       ("n_buffers", ctypes.c_int64), ("n_children", ctypes.c_int64),
+                       ("buffers", ctypes.POINTER(ctypes.c_void_p)),
+                       ("children", ctypes.POINTER(ctypes.POINTER(ArrowArray))),
+                       ("dictionary", ctypes.POINTER(ArrowArray)),
+                       ("release", ctypes.CFUNCTYPE(None, ctypes.POINTER(ArrowArray))),
+                       ("private_data", ctypes.c_void_p)]
+
+
+class ArrowDeviceArray(ctypes.Structure):
+    """struct ArrowDeviceArray of the Arrow C Device Data Interface"""
+    _fields_ = [("array", ArrowArray), ("device_id", ctypes.c_int64), ("device_type", ctypes.c_int32),
+                ("sync_event", ctypes.c_void_p), ("reserved", ctypes.c_int64 * 3)]
+
+
+ARROW_FLAG_DICTIONARY_ORDERED, ARROW_FLAG_NULLABLE, ARROW_FLAG_MAP_KEYS_SORTED = 1, 2, 4
+ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM = 1, 10
+ARROW_PLAIN, ARROW_DICT, ARROW_MAP = 0, 1, 2
+# the device validity kernel's tiles in rows (csrc/kernels.h ARROW_WAVE_ROWS / ARROW_BLOCK_ROWS: one lane takes 16 rows)
+ARROW_WAVE_ROWS, ARROW_BLOCK_ROWS = 1024, 4096
+
+
+class LpArrowCol(ctypes.Structure):
+    """lp_arrow_col (include/logparser_amd.h): one column of lp_result_arrow"""
+    _fields_ = [("path", ctypes.c_char_p), ("name", ctypes.c_char_p), ("form", ctypes.c_int32), ("kind", ctypes.c_int32)]
+
+
+ARROW_OWNER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
+
+
+class LpArrowOwner(ctypes.Structure):
+    """lp_arrow_owner: called once when the last exported array structure is released"""
+    _fields_ = [("free_fn", ARROW_OWNER_FN), ("ctx", ctypes.c_void_p)]
+
+
 def strings_from_dict(valid, index, dict_off, dict_chars):
     """The rows of a dictionary-encoded STRING column (lp_result_table_dict) as
     a list of str | None: row k is dictionary entry index[k] --
@@ -148,6 +199,9 @@ _TABLE_DEVICE_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values 
                         None: (ValueError, "lp_result_table (device) failed: %d")}
 _DICT_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use table_dict_from"),
                 None: (ValueError, "lp_result_table_dict failed: %d")}
+_ARROW_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use to_arrow"),
+                 LP_E_MISSING: (MissingDissectorsException, "lp_result_arrow: a path the parser does not deliver"),
+                 None: (ValueError, "lp_result_arrow failed: %d")}
 _MAP_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a map column's members are derived on the host only: use table_map_from"),
                LP_E_MISSING: (MissingDissectorsException, "lp_result_table_map: a path the parser does not deliver"),
                None: (ValueError, "lp_result_table_map failed: %d")}
@@ -245,6 +299,20 @@ def lib():
     L.lp_result_table_dict_rows.restype = ctypes.c_int
     L.lp_result_table_dict_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
                                             ctypes.POINTER(LpTableDictCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_arrow.restype = ctypes.c_int
+    L.lp_result_arrow.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_int64, ctypes.POINTER(LpArrowCol), ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ArrowSchema), ctypes.POINTER(ArrowDeviceArray)]
+    L.lp_arrow_from_tables.restype = ctypes.c_int
+    L.lp_arrow_from_tables.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(LpTableCol), c_char_pp, ctypes.c_int,
+                                       ctypes.POINTER(LpTableDictCol), c_char_pp, ctypes.c_int,
+                                       ctypes.POINTER(LpTableMapCol), c_char_pp, ctypes.c_int,
+                                       ctypes.POINTER(LpArrowOwner), ctypes.POINTER(ArrowSchema),
+                                       ctypes.POINTER(ArrowDeviceArray)]
+    L.lp_arrow_to_host.restype = ctypes.c_int
+    L.lp_arrow_to_host.argtypes = [ctypes.POINTER(ArrowSchema), ctypes.POINTER(ArrowDeviceArray),
+                                   ctypes.POINTER(ArrowArray)]
     L.lp_casts.restype = ctypes.c_int
     L.lp_casts.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     L.lp_describe.restype = ctypes.c_int64
@@ -316,6 +384,156 @@ def synth(workload, seed, first_line, n_lines):
     if nb < 0:
         raise ValueError("unknown synthetic workload %r" % workload)
     return buf.raw[:nb]
+
+
+class ArrowExport:
+    """One exported record batch (lp_result_arrow / lp_arrow_from_tables):
+    .schema (ArrowSchema) and .device_array (ArrowDeviceArray), the ctypes
+    structures a consumer of the Arrow C (Device) Data Interface takes by
+    address.  The batch lives until release() (or until a consumer that moved
+    the structures out releases them): it does not depend on the parser's next
+    batch or on the parser."""
+
+    def __init__(self, schema, device_array):
+        self.schema, self.device_array = schema, device_array
+        self._pa_schema = None
+
+    @property
+    def on_device(self):
+        return self.device_array.device_type != ARROW_DEVICE_CPU
+
+    def to_host_array(self):
+        """lp_arrow_to_host itself: the ArrowArray of a deep host copy (every
+        buffer byte for byte), the caller's to release; the export stays as it is."""
+        tmp = None
+        schema = self.schema
+        if self._pa_schema is not None:  # (to_host moved .schema into pyarrow: export that one)
+            schema = tmp = ArrowSchema()
+            self._pa_schema._export_to_c(ctypes.addressof(tmp))
+        out = ArrowArray()
+        try:
+            rc = lib().lp_arrow_to_host(ctypes.byref(schema), ctypes.byref(self.device_array), ctypes.byref(out))
+        finally:
+            if tmp is not None:
+                tmp.release(ctypes.byref(tmp))
+        if rc != LP_OK:
+            raise ValueError("lp_arrow_to_host failed: %d" % rc)
+        return out
+
+    def to_host(self):
+        """A pyarrow.RecordBatch of a deep host copy (lp_arrow_to_host); the
+        export itself stays as it is and may be copied again.  (The first call
+        moves .schema into a pyarrow.Schema, which later calls export again.)"""
+        import pyarrow as pa
+        out = self.to_host_array()
+        if self._pa_schema is None:
+            self._pa_schema = pa.Schema._import_from_c(ctypes.addressof(self.schema))
+        return pa.RecordBatch._import_from_c(ctypes.addressof(out), self._pa_schema)
+
+    def record_batch(self):
+        """The pyarrow.RecordBatch of a HOST export, without a copy: pyarrow
+        takes the structures over (this object is then released)."""
+        import pyarrow as pa
+        if self.on_device:
+            raise ValueError("a device export: use to_host()")
+        return pa.RecordBatch._import_from_c(ctypes.addressof(self.device_array.array), ctypes.addressof(self.schema))
+
+    def release(self):
+        """The release callbacks of whatever the consumer has not taken over"""
+        a = self.device_array.array
+        if a.release:
+            a.release(ctypes.byref(a))
+        if self.schema.release:
+            self.schema.release(ctypes.byref(self.schema))
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+_arrow_keep = {}  # owner context -> (what the exported buffers need alive, on_release)
+
+
+def _arrow_owner_release(ctx):
+    _, on_release = _arrow_keep.pop(ctx, (None, None))
+    if on_release is not None:
+        on_release()
+
+
+_arrow_owner_cb = ARROW_OWNER_FN(_arrow_owner_release)
+_arrow_next = [1]
+
+
+def _ptr(a):
+    """address of a numpy array / torch tensor (None: 0)"""
+    if a is None:
+        return None
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def arrow_from_tables(n_rows, plain=(), dicts=(), maps=(), device=-1, stream=None, on_release=None):
+    """lp_arrow_from_tables: wrap columns that already stand in numpy arrays
+    (device -1) or torch tensors of a device (device >= 0) into an ArrowExport
+    without copying a value buffer.
+      plain: [(name, str | int | float, valid, data[, path])] -- data the values
+             array, for str the pair (offsets int64 [n_rows + 1], chars uint8);
+             path (default: the name) "@line" makes the column large_binary;
+      dicts: [(name, valid, index int32, dict_off int64, dict_chars uint8)];
+      maps:  [(name, {MAP_ARRAYS name: array})] (an "entries_len" item overrides
+             len(key_off) - 1).
+    Children: the plain columns, the dictionary columns, the maps.  The arrays
+    are kept alive until the consumer has released the batch's last array
+    structure; on_release() is then called, once.  Raises ValueError(code)."""
+    kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
+    size = lambda a: int(a.numel()) if hasattr(a, "numel") else int(a.size)
+    names = lambda items: (ctypes.c_char_p * max(1, len(items)))(*[it[0].encode() for it in items])
+    P = (LpTableCol * max(1, len(plain)))()
+    for k, it in enumerate(plain):
+        name, typ, valid, data = it[:4]
+        c = P[k]
+        c.path = (it[4] if len(it) > 4 else name).encode()
+        c.kind = kinds[typ]
+        c.valid = _ptr(valid)
+        if typ is str:
+            c.i64, c.chars = _ptr(data[0]), _ptr(data[1])
+            c.chars_cap = c.chars_len = size(data[1])
+        elif typ is int:
+            c.i64 = _ptr(data)
+        else:
+            c.f64 = _ptr(data)
+    D = (LpTableDictCol * max(1, len(dicts)))()
+    for k, (name, valid, index, doff, dchars) in enumerate(dicts):
+        c = D[k]
+        c.path = name.encode()
+        c.valid, c.index, c.dict_off, c.dict_chars = _ptr(valid), _ptr(index), _ptr(doff), _ptr(dchars)
+        c.dict_cap = c.dict_len = size(doff) - 1
+        c.dict_chars_cap = c.dict_chars_len = size(dchars)
+    M = (LpTableMapCol * max(1, len(maps)))()
+    for k, (name, a) in enumerate(maps):
+        c = M[k]
+        c.path = name.encode()
+        c.valid, c.entry_off = _ptr(a["valid"]), _ptr(a["entry_off"])
+        c.key_off, c.val_off = _ptr(a["key_off"]), _ptr(a["val_off"])
+        c.key_chars, c.val_chars = _ptr(a["key_chars"]), _ptr(a["val_chars"])
+        c.entries_cap = c.entries_len = a.get("entries_len", size(a["key_off"]) - 1)
+        c.key_chars_cap = c.key_chars_len = size(a["key_chars"])
+        c.val_chars_cap = c.val_chars_len = size(a["val_chars"])
+    ctx = _arrow_next[0]
+    _arrow_next[0] += 1
+    _arrow_keep[ctx] = ((list(plain), list(dicts), list(maps)), on_release)
+    owner = LpArrowOwner(_arrow_owner_cb, ctx)
+    schema, dev = ArrowSchema(), ArrowDeviceArray()
+    rc = lib().lp_arrow_from_tables(device, ctypes.c_void_p(stream) if stream is not None else None, n_rows,
+                                    P, names(plain), len(plain), D, names(dicts), len(dicts), M, names(maps), len(maps),
+                                    ctypes.byref(owner), ctypes.byref(schema), ctypes.byref(dev))
+    if rc != LP_OK:
+        _arrow_keep.pop(ctx, None)  # (a failed call leaves the buffers the caller's: the owner is not called)
+        err = ValueError("lp_arrow_from_tables failed: %d" % rc)
+        err.code, err.schema, err.device_array = rc, schema, dev
+        raise err
+    return ArrowExport(schema, dev)
 
 
 class BatchResult:
@@ -781,6 +999,55 @@ class BatchResult:
         its columns: {"count": k_map_count and the piece-base scan, "entries":
         k_map_entries and its scans, "fill": k_map_fill and k_map_chars}"""
         return dict(zip(("count", "entries", "fill"), self._timing(8, 11)))
+
+    def arrow_call(self, res, columns, first=0, count=None, rows_p=None, threads=16):
+        """lp_result_arrow itself: (code, ArrowSchema, ArrowDeviceArray).
+        columns: [(path, str | int | float | "dict" | "map"[, field name])];
+        rows_p: the address of a row list (then count is its length)."""
+        kinds = {str: CAST_STRING, int: CAST_LONG, float: CAST_DOUBLE}
+        cols = (LpArrowCol * max(1, len(columns)))()
+        for k, col in enumerate(columns):
+            path, typ = col[0], col[1]
+            c = cols[k]
+            c.path = path.encode()
+            c.name = col[2].encode() if len(col) > 2 and col[2] is not None else None
+            c.form = ARROW_DICT if typ == "dict" else ARROW_MAP if typ == "map" else ARROW_PLAIN
+            c.kind = kinds.get(typ, 0)
+        count = self.n_lines - first if count is None else count
+        schema, dev = ArrowSchema(), ArrowDeviceArray()
+        rc = lib().lp_result_arrow(self._p._h, ctypes.byref(res), rows_p, first, count, cols, len(columns), threads,
+                                   ctypes.byref(schema), ctypes.byref(dev))
+        return rc, schema, dev
+
+    def _arrow(self, res, columns, first, count, rows, threads, device):
+        rows_p, first, count = self._window(rows, first, count, device)
+        rc, schema, dev = self.arrow_call(res, columns, first, count, rows_p, threads)
+        if rc != LP_OK:
+            exc, msg = _ARROW_ERRORS.get(rc) or _ARROW_ERRORS[None]
+            raise exc(msg % rc if rc not in _ARROW_ERRORS else msg)
+        return ArrowExport(schema, dev)
+
+    def to_arrow(self, res, columns, first=0, count=None, rows=None, threads=16):
+        """lp_result_arrow from a host copy: rows [first, first+count) -- or the
+        lines of rows (a numpy int64 array) -- as a pyarrow.RecordBatch, imported
+        through the Arrow C Data Interface without a further copy.  columns:
+        [(path, str | int | float | "dict" | "map"[, field name])]: typed
+        columns (pseudo-columns included; "@line" is large_binary),
+        dictionary-encoded STRING columns, wildcard map columns."""
+        import pyarrow  # noqa: F401  (ImportError here and nowhere else)
+        return self._arrow(res, columns, first, count, rows, threads, False).record_batch()
+
+    def to_arrow_device(self, columns, first=0, count=None, rows=None):
+        """lp_result_arrow on the device view: an ArrowExport whose buffers are
+        memory of the handle's device (ARROW_DEVICE_ROCM), bitmaps and int32 map
+        offsets made on the GPU; rows: a torch int64 tensor on the device.  It
+        outlives the parser's next batch and the parser: .to_host() a
+        pyarrow.RecordBatch, .release() when done."""
+        return self._arrow(self._view(), columns, first, count, rows, 0, True)
+
+    def arrow_timing(self):
+        """HIP-event ms of the last device lp_result_arrow's packaging kernels (lp_last_timing [16])"""
+        return self._timing(16, 17)[0]
 
     def record_json_from(self, res, i):
         """lp_result_record_json: the record of line i from a host copy."""

@@ -4,9 +4,11 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <cmath>
 #include <regex>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <memory>
 #include <string>
@@ -15,6 +17,7 @@
 
 #include "../../include/logparser_amd.h"
 #include "kernels.h"
+#include "lp_arrow.h"
 #include "lp_fixed.h"
 #include "plan.h"
 
@@ -124,7 +127,7 @@ bool read_back(hipStream_t s, V* dst, const void* src) {
 }
 
 // where each family's phases start in lp_handle::tms (lp_last_timing index - 5)
-enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7 };
+enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7, TMS_ARROW = 11 };
 
 }  // namespace
 
@@ -160,10 +163,11 @@ struct lp_handle {
     int64_t next_line = 0;         // ... of the next batch's (lp_parse_batch continues the numbering)
     hipEvent_t ev[5]{};  // batch start, index done, parse start, batch end, parse kernels done
     hipEvent_t tev[6]{}; // the device table calls' phase events (PhaseTimer): one pool, the calls are serialised
-    // lp_last_timing [5..15], each family's last successful device call: the table's values / scans /
+    // lp_last_timing [5..16], each family's last successful device call: the table's values / scans /
     // bytes phases; the map columns' count / entries / fill phases, summed over the columns;
-    // lp_result_select's passes and scan; the dictionary columns' four phases, summed over the columns
-    float tms[11]{};
+    // lp_result_select's passes and scan; the dictionary columns' four phases, summed over the columns;
+    // [16] lp_result_arrow's packaging kernels
+    float tms[12]{};
     int dict_hash_bits = 0;  // LP_OPT_DICT_HASH_BITS (tests: 0 = the whole hash)
     bool have_events = false;
     uint64_t counters[4]{};
@@ -960,7 +964,9 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     if (st != LP_OK) return st;
     for (int k = 0; k < n && k < 5; ++k) out[k] = h->ms[k];
     for (int k = 5; k < n && k < 16; ++k) out[k] = h->tms[k - 5];
-    return n < 16 ? n : 16;
+    if (n < 17) return n < 16 ? n : 16;  // (a caller of the 16 values sees what it always saw)
+    out[16] = h->tms[TMS_ARROW];
+    return 17;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1840,6 +1846,201 @@ int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t co
     for (int64_t i = first; i < first + count; ++i)
         if (selected(i)) rows[n++] = i;
     return LP_OK;
+}
+
+// ---- Arrow C Data Interface export (arrow_export.cpp, lp_arrow.h)
+namespace {
+// Every buffer of one exported batch (malloc on a host copy, hipMalloc on a
+// device view): the context of the owner the packaging calls when the
+// consumer has released the batch's last structure
+struct ArrowBufs {
+    bool host = true;
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        if (bytes == 0) bytes = 64;  // (never a null buffer, even without elements)
+        if (host) q = malloc(bytes);
+        else if (hipMalloc(&q, bytes) != hipSuccess) q = nullptr;
+        if (q) p.push_back(q);
+        return q;
+    }
+    ~ArrowBufs() {
+        for (void* q : p) {
+            if (host) free(q);
+            else (void)hipFree(q);
+        }
+    }
+};
+void arrow_bufs_free(void* ctx) { delete static_cast<ArrowBufs*>(ctx); }
+
+// A table family's call with its size protocol: after LP_E_NOMEM grow() makes
+// what the reported lengths ask for (false: no memory) and the call runs once more
+int arrow_sized(const std::function<int()>& call, const std::function<bool()>& grow) {
+    int st = call();
+    if (st == LP_E_NOMEM) st = grow() ? call() : LP_E_NOMEM;
+    return st;
+}
+}  // namespace
+
+static int result_arrow(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t first, int64_t count,
+                        const lp_arrow_col* cols, int n_cols, int threads, ArrowSchema* schema_out,
+                        ArrowDeviceArray* array_out) {
+    if (!h || !r || !cols || n_cols <= 0 || !schema_out || !array_out) return LP_E_INVALID;
+    if (rows) {
+        first = 0;
+        if (!rows_arg(rows, count)) return LP_E_INVALID;
+    }
+    // (the table calls check the window again; here it bounds what is allocated)
+    if (count < 0 || ((r->on_host || view_current(h, r)) && !check_window(first, count, rows, r->on_host ? r->n_lines : h->n_lines)))
+        return LP_E_INVALID;
+    // the columns by family, and where each stands in the batch
+    std::vector<lp_table_col> P;
+    std::vector<lp_table_dict_col> D;
+    std::vector<lp_table_map_col> M;
+    std::vector<const char*> pn, dn, mn;
+    std::vector<int> slot((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) {
+        const lp_arrow_col& A = cols[c];
+        if (!A.path) return LP_E_INVALID;
+        if (A.form == LP_ARROW_PLAIN) {
+            lp_table_col t{};
+            t.path = A.path;
+            t.kind = A.kind;
+            slot[(size_t)c] = (int)P.size();
+            P.push_back(t);
+            pn.push_back(A.name);
+        } else if (A.form == LP_ARROW_DICT) {
+            lp_table_dict_col t{};
+            t.path = A.path;
+            slot[(size_t)c] = (int)D.size();
+            D.push_back(t);
+            dn.push_back(A.name);
+        } else if (A.form == LP_ARROW_MAP) {
+            lp_table_map_col t{};
+            t.path = A.path;
+            slot[(size_t)c] = (int)M.size();
+            M.push_back(t);
+            mn.push_back(A.name);
+        } else {
+            return LP_E_INVALID;
+        }
+    }
+    const int nP = (int)P.size(), nD = (int)D.size(), nM = (int)M.size();
+    std::vector<int> order((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c)
+        order[(size_t)c] = slot[(size_t)c] + (cols[c].form == LP_ARROW_PLAIN ? 0 : cols[c].form == LP_ARROW_DICT ? nP : nP + nD);
+    const bool host = r->on_host != 0;
+    auto B = std::make_unique<ArrowBufs>();
+    B->host = host;
+    if (!host) hipSetDevice(h->device);
+    const size_t n1 = (size_t)count;
+    bool mem = true;
+    auto get = [&](auto*& dst, size_t bytes) {
+        dst = static_cast<std::remove_reference_t<decltype(dst)>>(B->get(bytes));
+        if (!dst) mem = false;
+    };
+    for (lp_table_col& C : P) {
+        get(C.valid, n1);
+        if (C.kind == LP_CAST_DOUBLE) get(C.f64, 8 * n1);
+        else get(C.i64, 8 * (n1 + 1));
+    }
+    for (lp_table_dict_col& C : D) {
+        get(C.valid, n1);
+        get(C.index, 4 * n1);
+        get(C.dict_off, 8);
+    }
+    for (lp_table_map_col& C : M) {
+        get(C.valid, n1);
+        get(C.entry_off, 8 * (n1 + 1));
+        get(C.key_off, 8);
+        get(C.val_off, 8);
+    }
+    if (!mem) return LP_E_NOMEM;
+    // the tables' own paths fill them: their checks, their codes, their size protocol
+    if (nP) {
+        const int st = arrow_sized([&] { return table_any(h, r, first, count, rows, P.data(), nP, threads); },
+                                   [&] {
+                                       for (lp_table_col& C : P)
+                                           if (C.kind == LP_CAST_STRING && C.chars_len > C.chars_cap) {
+                                               get(C.chars, (size_t)C.chars_len);
+                                               C.chars_cap = C.chars_len;
+                                           }
+                                       return mem;
+                                   });
+        if (st != LP_OK) return st;
+        for (lp_table_col& C : P)
+            if (C.kind == LP_CAST_STRING && !C.chars) get(C.chars, 0);
+    }
+    if (nD) {
+        const int st = arrow_sized([&] { return table_dict_any(h, r, first, count, rows, D.data(), nD, threads); },
+                                   [&] {
+                                       for (lp_table_dict_col& C : D) {
+                                           if (C.dict_len > C.dict_cap) {
+                                               get(C.dict_off, 8 * ((size_t)C.dict_len + 1));
+                                               C.dict_cap = C.dict_len;
+                                           }
+                                           if (C.dict_chars_len > C.dict_chars_cap) {
+                                               get(C.dict_chars, (size_t)C.dict_chars_len);
+                                               C.dict_chars_cap = C.dict_chars_len;
+                                           }
+                                       }
+                                       return mem;
+                                   });
+        if (st != LP_OK) return st;
+        for (lp_table_dict_col& C : D)
+            if (!C.dict_chars) get(C.dict_chars, 0);
+    }
+    if (nM) {
+        bool too_long = false;  // Arrow's map has int32 offsets
+        const int st = arrow_sized([&] { return table_map_any(h, r, first, count, rows, M.data(), nM, threads); },
+                                   [&] {
+                                       for (lp_table_map_col& C : M) {
+                                           if (C.entries_len > 0x7FFFFFFFull) return !(too_long = true);
+                                           if (C.entries_len > C.entries_cap) {
+                                               get(C.key_off, 8 * ((size_t)C.entries_len + 1));
+                                               get(C.val_off, 8 * ((size_t)C.entries_len + 1));
+                                               C.entries_cap = C.entries_len;
+                                           }
+                                           if (C.key_chars_len > C.key_chars_cap) {
+                                               get(C.key_chars, (size_t)C.key_chars_len);
+                                               C.key_chars_cap = C.key_chars_len;
+                                           }
+                                           if (C.val_chars_len > C.val_chars_cap) {
+                                               get(C.val_chars, (size_t)C.val_chars_len);
+                                               C.val_chars_cap = C.val_chars_len;
+                                           }
+                                       }
+                                       return mem;
+                                   });
+        if (too_long) return LP_E_INVALID;
+        if (st != LP_OK) return st;
+        for (lp_table_map_col& C : M) {
+            if (!C.key_chars) get(C.key_chars, 0);
+            if (!C.val_chars) get(C.val_chars, 0);
+        }
+    }
+    if (!mem) return LP_E_NOMEM;
+    // the packaging wraps them; the owner frees them when the consumer is done
+    const lp_arrow_owner owner{arrow_bufs_free, B.get()};
+    float ms = 0;
+    const int st = lp::arrow_wrap(host ? -1 : h->device, h->stream, count, P.data(), pn.data(), nP, D.data(), dn.data(), nD,
+                                  M.data(), mn.data(), nM, order.data(), &owner, schema_out, array_out, host ? nullptr : &ms);
+    if (st != LP_OK) return st;  // (the owner was not called: B frees the buffers)
+    B.release();
+    if (!host && count > 0) h->tms[TMS_ARROW] = ms;  // (an empty export launches no bitmap kernel and keeps the last figure)
+    return LP_OK;
+}
+
+int lp_result_arrow(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t first, int64_t count,
+                    const lp_arrow_col* cols, int n_cols, int threads, ArrowSchema* schema_out,
+                    ArrowDeviceArray* array_out) {
+    if (schema_out) memset(schema_out, 0, sizeof *schema_out);
+    if (array_out) memset(array_out, 0, sizeof *array_out);
+    try {
+        return result_arrow(h, r, rows, first, count, cols, n_cols, threads, schema_out, array_out);
+    } catch (const std::bad_alloc&) {
+        return LP_E_NOMEM;
+    }
 }
 
 int lp_result_emit(lp_handle* h, const lp_result* r, int64_t i, lp_emit_fn fn, void* ctx) {

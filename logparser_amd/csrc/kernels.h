@@ -181,4 +181,26 @@ int launch_select_count(const uint8_t* status, int64_t first, int64_t count, uin
 int launch_select_write(const uint8_t* status, int64_t first, int64_t count, uint32_t mask, int64_t* rows, void* scratch,
                         size_t scratch_bytes, hipStream_t s);
 
+// The Arrow export's packaging on device memory (arrow.hip).
+//   launch_arrow_validity  n_cols columns' valid bytes [n_rows] (n_rows > 0; any
+//                          alignment) -> their validity bitmaps, each ((n_rows +
+//                          7) / 8 rounded up to 64) bytes, all written, and the
+//                          count of valid rows ADDED to *count (the caller zeroes
+//                          it on the stream before).  One lane takes 16 rows, one
+//                          wave ARROW_WAVE_ROWS, one block ARROW_BLOCK_ROWS.
+//   launch_arrow_narrow32  out[k] = (int32) in[k], k < n (n > 0)
+constexpr int ARROW_WAVE_ROWS = 1024;
+constexpr int ARROW_BLOCK_ROWS = 4096;
+constexpr int ARROW_MAX_COLS = 32;  // columns per launch (the argument table travels as the kernel's argument)
+struct ArrowValidCol {
+    const uint8_t* valid;
+    uint8_t* bitmap;
+    unsigned long long* count;
+};
+struct ArrowValidArgs {
+    ArrowValidCol col[ARROW_MAX_COLS];
+};
+int launch_arrow_validity(const ArrowValidArgs& A, int n_cols, int64_t n_rows, hipStream_t s);
+int launch_arrow_narrow32(const int64_t* in, int32_t* out, int64_t n, hipStream_t s);
+
 }  // namespace lp
