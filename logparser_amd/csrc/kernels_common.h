@@ -24,6 +24,7 @@ constexpr int NL_THREADS = 256;   // 256 threads x 16 B x 16 iterations = 64 KiB
 constexpr int PW = 64;            // lanes per wave = lines per parse wave
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // exact per-byte "== c" mask of a 32-bit word (high bit of each byte)
 __device__ __forceinline__ uint32_t byte_eq(uint32_t w, uint32_t c4) {

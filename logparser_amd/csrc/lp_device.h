@@ -327,6 +327,32 @@ __host__ __device__ LP_INLINE void classify16c(uint32_t w0, uint32_t w1, uint32_
     }
     cr = pack16(c[0], c[1], c[2], c[3]);
 }
+// One whole 64-byte mask block (16 little-endian words), the unit a lane of
+// the chunk kernel's staging pass takes: four classify16p on independent
+// registers.  p0 / p1 / lf = the block's QUOTE and WS plane words and its
+// '\n' bytes (byte i of the block -> bit i: the words build_masks makes),
+// g[j] = the guard word of 16-byte piece j (classify16p's bad: bit 8 i + 7
+// set when one of the piece's bytes i, i + 4, i + 8, i + 12 is >= 0x7F),
+// other = the same per-word byte columns of the whole block holding a control
+// byte other than '\n' (rare; the caller resolves them with classify16c).
+struct Block64 {
+    uint64_t p0, p1, lf;
+    uint32_t g[4];
+    uint32_t other;
+};
+__host__ __device__ LP_INLINE Block64 classify64p(const uint32_t (&w)[16]) {
+    Block64 K;
+    uint32_t a[4], b[4], l[4], o[4];
+    LP_UNROLL for (int j = 0; j < 4; ++j) {
+        K.g[j] = 0;
+        classify16p(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3], a[j], b[j], K.g[j], l[j], o[j]);
+    }
+    K.p0 = (uint64_t)(a[0] | (a[1] << 16)) | ((uint64_t)(a[2] | (a[3] << 16)) << 32);
+    K.p1 = (uint64_t)(b[0] | (b[1] << 16)) | ((uint64_t)(b[2] | (b[3] << 16)) << 32);
+    K.lf = (uint64_t)(l[0] | (l[1] << 16)) | ((uint64_t)(l[2] | (l[3] << 16)) << 32);
+    K.other = o[0] | o[1] | o[2] | o[3];
+    return K;
+}
 // mask class whose members are exactly the byte c, -1 none
 __host__ __device__ LP_INLINE int class_of(uint32_t c) { return c == '"' ? (int)MC_QUOTE : -1; }
 }  // namespace bcls

@@ -86,8 +86,10 @@ struct ChunkScan {
 // The bytes reach LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave
 // instruction, no registers held while they are in flight) when the window
 // is whole 1 KiB blocks inside the buffer, else (the batch's last chunk) by
-// plain loads; then one pass over the LDS copy classifies every 16 bytes
-// into the two mask planes and the line terminators.
+// plain loads; then one pass over the LDS copy, a lane taking one whole
+// 64-byte mask block per round (bcls::classify64p), makes the two mask planes
+// (one 16-byte store per block) and the line terminators: a round is 4 KiB,
+// and its starts are ranked once.
 __device__ __forceinline__ ChunkScan stage_chunk(const uint8_t* __restrict__ buf, uint64_t nbytes, uint64_t w0,
                                                  uint64_t w1, uint64_t t_lo, uint64_t t_hi, uint32_t first,
                                                  uint8_t* win, uint16_t* msk16, uint32_t* starts) {
@@ -99,6 +101,7 @@ __device__ __forceinline__ ChunkScan stage_chunk(const uint8_t* __restrict__ buf
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(buf + w0 + 16ull * (k0 + lane)),
                                              (__attribute__((address_space(3))) void*)(win + 16 * k0), 16, 0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        LP_PROF(63);  // (the window's DMA has landed: the rest of the stage classifies and ranks)
     } else {
         for (int k = lane; k < nv4; k += PW) {
             u32x4 v = u32x4{0, 0, 0, 0};
@@ -111,71 +114,85 @@ __device__ __forceinline__ ChunkScan stage_chunk(const uint8_t* __restrict__ buf
     // last) skip the boundary masks
     const uint32_t nrel = nbytes - w0 < 16ull * (uint64_t)(nv4 + 1) ? (uint32_t)(nbytes - w0) : 16u * (uint32_t)(nv4 + 1);
     const uint32_t tl = (uint32_t)(t_lo - w0), th = (uint32_t)(t_hi - w0);
+    const int nb = nv4 >> 2;     // 64-byte mask blocks: one per lane and round (4 KiB per round)
     uint32_t bad = 0;
     uint32_t run = first;        // starts numbered so far (wave-uniform)
     uint32_t end_rel = ~0u;      // this lane's first terminator >= t_hi (relative)
-    u32x4 vn = lane < nv4 ? *reinterpret_cast<const u32x4*>(win + 16 * lane) : u32x4{0, 0, 0, 0};
-    for (int k0 = 0; k0 < nv4; k0 += PW) {  // wave-uniform rounds: every lane joins the ballots
-        const int k = k0 + lane;
-        const uint32_t q = 16u * (uint32_t)k;
-        const uint32_t r0 = 16u * (uint32_t)k0, r1 = r0 + 16u * PW;
-        const bool inner = r0 >= tl && r1 <= th && r1 <= nrel && k0 + PW <= nv;  // wave-uniform
-        uint32_t tm = 0;
-        const u32x4 v = vn;
-        if (k + PW < nv4) vn = *reinterpret_cast<const u32x4*>(win + 16 * (k + PW));  // the next round's piece
-        if (k < nv4) {
-            uint32_t m0, m1, g = 0, lf, other;
-            bcls::classify16p(v[0], v[1], v[2], v[3], m0, m1, g, lf, other);
-            msk16[8 * (k >> 2) + (k & 3)] = (uint16_t)m0;
-            msk16[8 * (k >> 2) + 4 + (k & 3)] = (uint16_t)m1;
-            tm = lf;
-            if (other) {  // TAB, '\r' or another control byte (rare): the exact guard and CR terminators
-                uint32_t cr;
-                bcls::classify16c(v[0], v[1], v[2], v[3], g, cr);
+    u32x4 vn[4];
+    LP_UNROLL for (int j = 0; j < 4; ++j)
+        vn[j] = lane < nb ? *reinterpret_cast<const u32x4*>(win + 64 * lane + 16 * j) : u32x4{0, 0, 0, 0};
+    for (int b0 = 0; b0 < nb; b0 += PW) {  // wave-uniform rounds: every lane joins the ballots
+        const int B = b0 + lane;
+        const uint32_t q = 64u * (uint32_t)B;
+        const uint32_t r0 = 64u * (uint32_t)b0, r1 = r0 + 64u * PW;
+        const bool inner = r0 >= tl && r1 <= th && r1 <= nrel && 4 * (b0 + PW) <= nv;  // wave-uniform
+        uint64_t tm = 0;
+        uint32_t w[16];
+        LP_UNROLL for (int j = 0; j < 16; ++j) w[j] = vn[j >> 2][j & 3];
+        if (B + PW < nb) {  // the next round's block
+            LP_UNROLL for (int j = 0; j < 4; ++j) vn[j] = *reinterpret_cast<const u32x4*>(win + 64 * (B + PW) + 16 * j);
+        }
+        if (B < nb) {
+            bcls::Block64 K = bcls::classify64p(w);
+            // the block's planes as msk16 holds them: four u16 of plane 0, then four of plane 1
+            *reinterpret_cast<u64x2*>(msk16 + 8 * B) = u64x2{K.p0, K.p1};
+            tm = K.lf;
+            if (K.other) {  // TAB, '\r' or another control byte (rare): the exact guard and CR terminators
+                uint64_t cr = 0;
+                LP_UNROLL for (int j = 0; j < 4; ++j) {
+                    uint32_t c;
+                    bcls::classify16c(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3], K.g[j], c);
+                    cr |= (uint64_t)c << (16 * j);
+                }
                 if (cr) {
-                    // "\r\n": the '\n' ends the line; a lone '\r' does (term_bits)
+                    // "\r\n": the '\n' ends the line; a lone '\r' does (term_bits).  Only a
+                    // '\r' in the block's last byte looks past the lane's own registers
                     const uint64_t p = w0 + q;
-                    uint32_t next_lf = lf >> 1;
-                    if ((cr & 0x8000u) && p + 16 < nbytes && buf[p + 16] == '\n') next_lf |= 0x8000u;
+                    uint64_t next_lf = K.lf >> 1;
+                    if ((cr >> 63) && p + 64 < nbytes && buf[p + 64] == '\n') next_lf |= 1ull << 63;
                     tm |= cr & ~next_lf;
                 }
             }
             if (inner) {
-                bad |= g;
+                bad |= K.g[0] | K.g[1] | K.g[2] | K.g[3];
             } else {
-                if (k < nv) bad |= g;
-                if (q + 16 > nrel) tm &= nrel > q ? (1u << (nrel - q)) - 1u : 0u;
+                LP_UNROLL for (int j = 0; j < 4; ++j)
+                    if (4 * B + j < nv) bad |= K.g[j];
+                if (q + 64 > nrel) tm &= nrel > q ? (1ull << (nrel - q)) - 1ull : 0ull;
             }
         }
         // terminators in [t_lo, t_hi): line starts; the first at or after t_hi: the end
-        uint32_t ms = tm;
+        uint64_t ms = tm;
         if (!inner) {
-            uint32_t me = 0;
-            if (q < tl) ms &= tl - q >= 16 ? 0u : ~0u << (tl - q);
-            if (q + 16 > th) {
-                const uint32_t lo = th > q ? (1u << (th - q)) - 1u : 0u;
+            uint64_t me = 0;
+            if (q < tl) ms &= tl - q >= 64 ? 0ull : ~0ull << (tl - q);
+            if (q + 64 > th) {
+                const uint64_t lo = th > q ? (1ull << (th - q)) - 1ull : 0ull;
                 me = tm & ~lo;
                 ms &= lo;
             }
-            if (me) end_rel = min(end_rel, q + (uint32_t)__builtin_ctz(me));
+            if (me) end_rel = min(end_rel, q + (uint32_t)__builtin_ctzll(me));
         }
-        // rank of this lane's first start in the round: the counts (0..16) of
+        // rank of this lane's first start in the round: the counts (0..64) of
         // the lanes below it, bit plane by bit plane (ballot + mbcnt; no
-        // cross-lane permutes in the loop)
-        const uint32_t c = (uint32_t)__popc(ms);
-        const uint64_t b0 = __ballot(c & 1u), b1 = __ballot(c & 2u);
-        uint32_t excl = below(b0) + 2 * below(b1);
-        uint32_t tot = (uint32_t)(__popcll(b0) + 2 * __popcll(b1));
+        // cross-lane permutes in the loop).  A lane's starts are in position
+        // order and the lanes' blocks are, so the round's are in lane order
+        const uint32_t c = (uint32_t)__popcll(ms);
+        const uint64_t b0m = __ballot(c & 1u), b1m = __ballot(c & 2u);
+        uint32_t excl = below(b0m) + 2 * below(b1m);
+        uint32_t tot = (uint32_t)(__popcll(b0m) + 2 * __popcll(b1m));
         const uint64_t bh = __ballot(c >= 4u);
-        if (bh) {  // wave-uniform: a lane with 4 or more terminators in 16 bytes (short lines)
-            const uint64_t b2 = __ballot(c & 4u), b3 = __ballot(c & 8u), b4 = __ballot(c & 16u);
-            excl += 4 * below(b2) + 8 * below(b3) + 16 * below(b4);
-            tot += (uint32_t)(4 * __popcll(b2) + 8 * __popcll(b3) + 16 * __popcll(b4));
+        if (bh) {  // wave-uniform: a lane with 4 or more terminators in its 64 bytes (short lines)
+            LP_UNROLL for (int k = 2; k < 7; ++k) {
+                const uint64_t bk = __ballot(c & (1u << k));
+                excl += below(bk) << k;
+                tot += (uint32_t)__popcll(bk) << k;
+            }
         }
         uint32_t r = run + excl;
         run += tot;
-        for (uint32_t m = ms; m; m &= m - 1, ++r)
-            if (r < (uint32_t)MAXS) starts[r] = q + (uint32_t)__builtin_ctz(m) + 1u;
+        for (uint64_t m = ms; m; m &= m - 1, ++r)
+            if (r < (uint32_t)MAXS) starts[r] = q + (uint32_t)__builtin_ctzll(m) + 1u;
     }
     ChunkScan S;
     S.count = run;
