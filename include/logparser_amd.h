@@ -123,9 +123,11 @@ int64_t lp_possible_paths_remapped(const char *logformats, int max_depth, const 
                                   leaves the chunk to the deferred pass (0 = default 16384; -1: none,
                                   every chunk goes to the deferred pass; -2: the odd chunks go to it
                                   without polling, the even ones wait as by default) */
-#define LP_OPT_ONE_PASS 6      /* several LogFormats: 1 (default) one pass over the input (the chunk kernel
-                                  routes every line exactly one format matches; the rest after the
-                                  routing scan), 0 the line index, routing and parse passes */
+#define LP_OPT_ONE_PASS 6      /* reserved: every device program is parsed in one pass over the input
+                                  (several LogFormats: the chunk kernel routes every line exactly one
+                                  format matches; the rest after the routing scan).  1 is accepted and
+                                  changes nothing; 0, which once chose separate line index, routing
+                                  and parse passes, is LP_E_INVALID */
 #define LP_OPT_FIXED_SHAPE 7   /* 1 (default): a handle whose compiled program equals one of the fixed
                                   shapes (common, combined with every path requested) is parsed by
                                   that shape's instance of the chunk kernel, lp_counters out[11];
@@ -178,10 +180,10 @@ int64_t lp_line_offset(lp_handle *h, int64_t i);
  * is not OK, -100 - needed if cap is too small). */
 int64_t lp_line_record_json(lp_handle *h, int64_t i, char *out, size_t cap);
 /* out[0..3] = lines, ok, bad, fallback of the last batch (device counters);
- * diagnostics: out[4] = one LogFormat: lines parsed by the direct kernel (a
- * byte chunk's 65th line onwards, or a line ending past the chunk's LDS
- * window); several LogFormats: waves parsed by the overflow kernel (their
- * lines' window exceeded the main kernel's LDS window), out[5] = re-runs of the
+ * diagnostics: out[4] = lines the chunk kernel queued for the direct kernel,
+ * which reads them from HBM (a byte chunk's 65th line onwards, a line ending
+ * past the chunk's LDS window, and the lines out[9] counts; 0 when the
+ * program is not on the device), out[5] = re-runs of the
  * batch (capacity / arena estimates exceeded), out[6] = arena overflows the
  * final run left (lines sent to FALLBACK for want of arena; 0 normally),
  * out[7] = waves whose URI bytes exceeded the URI kernel's compact buffer
@@ -202,11 +204,12 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
 
 /* Device-side timing of the last batch, in milliseconds, measured with HIP
  * events on the batch's stream: [0] whole batch, [1] separate line index
- * kernels (0 for one-LogFormat programs after a handle's first batch: their
- * parse kernel finds the lines itself), [2] parse pass (every kernel after
- * the index), [3] of it the parse kernels (one LogFormat: k_parse_chunks +
- * k_parse_ovf_lines; several: routing match + k_parse_lines + its direct
- * path), [4] of it the URI kernels (+ the counter reduction); then the last
+ * kernels (a program that is not on the device; a device program's parse
+ * kernel finds the lines itself: only the line count of a prefix, on a
+ * handle's first batch without a reservation), [2] parse pass (every kernel
+ * after the index), [3] of it the parse kernels (k_parse_chunks and
+ * k_parse_ovf_lines; several LogFormats: k_route_ovf and the routing scan
+ * between them), [4] of it the URI kernels (+ the counter reduction); then the last
  * complete lp_result_table on a device view: [5] k_table_values, [6] the
  * STRING columns' offset scans, [7] k_table_chars; then the last complete
  * lp_result_table_map on a device view, summed over its columns: [8]

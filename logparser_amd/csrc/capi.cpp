@@ -173,11 +173,9 @@ struct lp_handle {
     uint64_t counters[4]{};
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
     int32_t chunk_wait = 0;        // LP_OPT_CHUNK_WAIT (tests: 0 default, < 0 defer every chunk not yet reached)
-    bool one_pass = true;          // LP_OPT_ONE_PASS: several LogFormats on the chunked one-pass path
     bool fixed_shape = true;       // LP_OPT_FIXED_SHAPE: the chunk kernel's fixed-shape instances (lp_fixed.h)
-    bool chunked = false;          // the last batch ran the chunked parse (line index inside the parse kernel)
-    uint64_t ovf_waves = 0;        // waves of the last batch parsed by k_parse_overflow (chunked: lines by k_parse_ovf_lines)
-    uint64_t uri_ovf_waves = 0;    // ... whose URI stages ran in k_uri_overflow
+    uint64_t ovf_lines = 0;        // lines of the last batch the chunk kernel queued for k_parse_ovf_lines
+    uint64_t uri_ovf_waves = 0;    // waves of the last batch whose URI stages ran in k_uri_overflow
     uint64_t deferred = 0;         // chunks of the last batch parsed by the deferred pass (normally 0)
     uint64_t dfs_lines = 0;        // lines of the last batch the chunk kernel queued for the backtracking DFS
     uint64_t uri_fix_lines = 0;    // lines of the last batch whose URI stages were redone with the repair on (uri_redo_line)
@@ -360,12 +358,12 @@ bool simple_program(const lp::Program& P) {
 
 // The fixed shape (lp_fixed.h) whose chunk kernel instance parses P: only
 // when every field that instance holds as a constant equals P's, field by
-// field (fixed_shape_of), and P is on the chunked one-pass path with its
-// lines in LDS.  Near-miss formats, requested-field subsets that change the
-// capture slots or stage lists, several LogFormats and LP_OPT_FORCE_DIRECT
-// get FS_NONE: today's instances.
-int fixed_shape_program(const lp::Program& P, bool chunked, bool force_direct) {
-    if (!chunked || force_direct || !simple_program(P)) return lp::FS_NONE;
+// field (fixed_shape_of), and its lines are in LDS.  Near-miss formats,
+// requested-field subsets that change the capture slots or stage lists,
+// several LogFormats and LP_OPT_FORCE_DIRECT get FS_NONE: the instances per
+// program class.
+int fixed_shape_program(const lp::Program& P, bool force_direct) {
+    if (force_direct || !simple_program(P)) return lp::FS_NONE;
     return lp::fixed_shape_of(P);
 }
 
@@ -383,15 +381,11 @@ int enqueue(lp_handle* h, bool sync_count) {
     if (hipMemsetAsync(d_meta, 0, sizeof(lp::Meta), s) != hipSuccess) return LP_E_DEVICE;
     hipEventRecord(h->ev[0], s);
     int64_t cap = h->cap_lines;
-    // one LogFormat: the parse kernel finds the lines itself (k_parse_chunks);
-    // several: the routing pass needs the line index first
-    // one pass: the parse kernel finds the lines itself (k_parse_chunks);
-    // several LogFormats route inside it too (LP_OPT_ONE_PASS 0: the line
-    // index, the routing passes, then the parse)
-    const bool chunked = h->plan.device_ok() && (P.n_fmt == 1 || h->one_pass);
-    h->chunked = chunked;
-    if (sync_count && chunked) {
-        // first batch of a one-format handle: the line length of an 8 MiB
+    // a device program: the parse kernel finds the lines itself
+    // (k_parse_chunks); any other needs the line index built here
+    const bool device = h->plan.device_ok();
+    if (sync_count && device) {
+        // first batch of a handle: the line length of an 8 MiB
         // prefix sizes the columns (no pass over the whole input; a short
         // estimate sets cap_ovf and finish() re-runs with the exact count)
         const uint64_t pre = std::min<uint64_t>(nbytes, 8ull << 20);
@@ -406,7 +400,7 @@ int enqueue(lp_handle* h, bool sync_count) {
         cap = std::max<int64_t>(headroom((int64_t)((double)nbytes / mean * 1.02)), h->reserve_lines);
         h->mean_line = mean;  // sizes this batch's LDS windows
     } else if (sync_count) {
-        // first batch of a handle: the exact line count sizes the columns
+        // first batch of a handle whose program is not on the device: the exact line count sizes the columns
         if (!h->line_off.ensure(16)) return LP_E_NOMEM;
         if (lp::launch_count(h->d_buf, nbytes, d_chunk, d_nlmask, h->line_off.as<uint64_t>(), -1, d_meta, s) != 0)
             return LP_E_DEVICE;
@@ -417,13 +411,13 @@ int enqueue(lp_handle* h, bool sync_count) {
         // headroom for the next batches of the stream (sized like the estimate below)
         cap = std::max<int64_t>(headroom((int64_t)n), h->reserve_lines);
         if (n) h->mean_line = (double)nbytes / (double)n;  // sizes this batch's LDS windows
-    } else if (!chunked) {
+    } else if (!device) {
         if (!h->line_off.ensure(sizeof(uint64_t) * (size_t)(cap + 2))) return LP_E_NOMEM;
         if (lp::launch_count(h->d_buf, nbytes, d_chunk, d_nlmask, h->line_off.as<uint64_t>(), cap, d_meta, s) != 0)
             return LP_E_DEVICE;
     }
     if (!h->line_off.ensure(sizeof(uint64_t) * (size_t)(cap + 2))) return LP_E_NOMEM;
-    if (sync_count && !chunked) {  // the scan ran without the line index buffer: its ends now
+    if (sync_count && !device) {  // the scan ran without the line index buffer: its ends now
         unsigned long long n = 0;
         hipMemcpy(&n, &d_meta->n_lines, sizeof n, hipMemcpyDeviceToHost);
         uint64_t ends[2] = {0, nbytes + 1};
@@ -433,7 +427,7 @@ int enqueue(lp_handle* h, bool sync_count) {
         if (nbytes && last != '\n' && last != '\r') hipMemcpy(h->line_off.as<uint64_t>() + n, &ends[1], 8, hipMemcpyHostToDevice);
     }
     h->cap_lines = cap;
-    if (!chunked && lp::launch_offsets(d_nlmask, nbytes, d_chunk, h->line_off.as<uint64_t>(), cap, s) != 0)
+    if (!device && lp::launch_offsets(d_nlmask, nbytes, d_chunk, h->line_off.as<uint64_t>(), cap, s) != 0)
         return LP_E_DEVICE;
     hipEventRecord(h->ev[1], s);
     if (!alloc_columns(h, cap)) return LP_E_NOMEM;
@@ -442,7 +436,7 @@ int enqueue(lp_handle* h, bool sync_count) {
     const double per = h->arena_per_line > 0 ? h->arena_per_line * 1.25 : 64.0;
     uint64_t acap = std::max<uint64_t>(h->reserve_arena, (uint64_t)(per * (double)cap) + (1u << 20));
     if (h->arena_first && h->retries == 0) acap = h->arena_first;
-    if (!h->plan.device_ok() || !P.has_phase2()) acap = 4096 * LP_ARENA_SHARDS;
+    if (!device || !P.has_phase2()) acap = 4096 * LP_ARENA_SHARDS;
     h->shard_cap = (acap / LP_ARENA_SHARDS + 255) & ~255ull;
     if (!h->arena.ensure(h->shard_cap * LP_ARENA_SHARDS)) return LP_E_NOMEM;
     lp::Columns& C = h->C;
@@ -453,12 +447,11 @@ int enqueue(lp_handle* h, bool sync_count) {
     C.cap_lines = cap;
     const int64_t waves = lp::parse_waves(cap);
     if (!h->waves.ensure(4 * lp::WC_WORDS * (size_t)(waves + 1))) return LP_E_NOMEM;
-    if (!h->ovf.ensure(8 * (size_t)(waves + 1) + 4 * (size_t)(cap + 1))) return LP_E_NOMEM;
+    if (!h->ovf.ensure(4 * (size_t)(waves + 1) + 4 * (size_t)(cap + 1))) return LP_E_NOMEM;
     C.wave_counts = h->waves.as<uint32_t>();
-    C.ovf_list = h->ovf.as<uint32_t>();
-    C.uri_ovf_list = h->ovf.as<uint32_t>() + (waves + 1);
-    C.uri_fix_list = h->ovf.as<uint32_t>() + 2 * (waves + 1);  // one entry per line
-    if (h->plan.device_ok()) {
+    C.uri_ovf_list = h->ovf.as<uint32_t>();
+    C.uri_fix_list = h->ovf.as<uint32_t>() + (waves + 1);  // one entry per line
+    if (device) {
         if (P.n_fmt > 1) {  // sticky multi-format routing scratch
             if (!h->route.ensure(8 * (size_t)(lp::fmt_chunks(cap) + 1))) return LP_E_NOMEM;
             C.fmt_chunk = h->route.as<uint64_t>();
@@ -470,10 +463,9 @@ int enqueue(lp_handle* h, bool sync_count) {
                            h->ev[4]};
         for (int u = 0; u < P.n_uri; ++u) pl.derived = pl.derived || P.uri[u].src_q >= 0;
         if (!pl.mean_line && cap > 0) pl.mean_line = (nbytes + cap - 1) / (uint64_t)cap;
-        pl.chunked = chunked;
         pl.chunk_lines = h->chunk_lines;
         pl.chunk_wait = h->chunk_wait;
-        pl.multi = chunked && P.n_fmt > 1;
+        pl.multi = P.n_fmt > 1;
         pl.lit_aware = false;
         for (int i = 0; i < P.n_elems; ++i) {
             const lp::ElemV e = lp::load_elem(P.elems + i);
@@ -481,32 +473,24 @@ int enqueue(lp_handle* h, bool sync_count) {
                 pl.lit_aware = true;
         }
         pl.simple = simple_program(P);
-        pl.shape = h->fixed_shape && !pl.lit_aware ? fixed_shape_program(P, chunked, h->force_direct) : lp::FS_NONE;
+        pl.shape = h->fixed_shape && !pl.lit_aware ? fixed_shape_program(P, h->force_direct) : lp::FS_NONE;
         h->last_launch = pl;
-        if (chunked) {
-            // look-back words (zeroed), per-chunk counts, the queued line list
-            const lp::ChunkPlan cp = lp::chunk_plan(pl);
-            const size_t sb = align256(8 * (size_t)(cp.n_chunks + 1)), cb = align256(4 * lp::WC_WORDS * (size_t)(cp.n_chunks + 1));
-            const size_t ob = align256(4 * (size_t)(cap + 1));
-            if (!h->cstate.ensure(sb + cb + ob + 4 * (size_t)(cp.n_chunks + 1))) return LP_E_NOMEM;
-            C.chunk_state = h->cstate.as<uint64_t>();
-            C.chunk_counts = h->cstate.as<uint32_t>(sb);
-            C.ovf_lines = h->cstate.as<uint32_t>(sb + cb);
-            C.deferred_chunks = h->cstate.as<uint32_t>(sb + cb + ob);
-            if (hipMemsetAsync(C.chunk_state, 0, sb, s) != hipSuccess) return LP_E_DEVICE;
-        }
+        // look-back words (zeroed), per-chunk counts, the queued line list
+        const lp::ChunkPlan cp = lp::chunk_plan(pl);
+        const size_t sb = align256(8 * (size_t)(cp.n_chunks + 1)), cb = align256(4 * lp::WC_WORDS * (size_t)(cp.n_chunks + 1));
+        const size_t ob = align256(4 * (size_t)(cap + 1));
+        if (!h->cstate.ensure(sb + cb + ob + 4 * (size_t)(cp.n_chunks + 1))) return LP_E_NOMEM;
+        C.chunk_state = h->cstate.as<uint64_t>();
+        C.chunk_counts = h->cstate.as<uint32_t>(sb);
+        C.ovf_lines = h->cstate.as<uint32_t>(sb + cb);
+        C.deferred_chunks = h->cstate.as<uint32_t>(sb + cb + ob);
+        if (hipMemsetAsync(C.chunk_state, 0, sb, s) != hipSuccess) return LP_E_DEVICE;
         h->host_args.prog = P;
         h->host_args.cols = C;
         if (hipMemcpyAsync(h->args.p, &h->host_args, sizeof(lp::DeviceArgs), hipMemcpyHostToDevice, s) != hipSuccess)
             return LP_E_DEVICE;
         hipEventRecord(h->ev[2], s);
         const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
-        if (P.n_fmt > 1 && !chunked) {
-            // HttpdLogFormatDissector routing: every format's match per line,
-            // then the scan of the sticky active format (one pass: inside
-            // launch_parse, after the chunk kernel)
-            if (lp::launch_route_match(pl, d_args, s) != 0 || lp::launch_route(d_args, cap, s) != 0) return LP_E_DEVICE;
-        }
         if (lp::launch_parse(pl, d_args, C, s) != 0) return LP_E_DEVICE;
     } else {
         // the requested paths need a dissector that is not on the device:
@@ -581,10 +565,10 @@ int finish(lp_handle* h) {
             for (int k = 0; k < 4; ++k) h->counters[k] = m.counters[k];
             h->arena_written = m.counters[4];
             h->uri_src_bytes = m.counters[5];
-            h->ovf_waves = h->chunked ? m.ovf_lines : m.ovf_waves;
+            h->ovf_lines = m.ovf_lines;
             h->uri_ovf_waves = m.uri_ovf_waves;
-            h->deferred = h->chunked ? m.deferred : 0;
-            h->dfs_lines = h->chunked ? m.dfs_lines : 0;
+            h->deferred = m.deferred;
+            h->dfs_lines = m.dfs_lines;
             h->uri_fix_lines = (m.uri_fix_lines & 0xFFFFFFFFull) + (m.uri_fix_lines >> 32);  // the queued ones, k_uri_overflow's own
         } else {
             h->counters[0] = (uint64_t)n;
@@ -776,9 +760,7 @@ int lp_set_option(lp_handle* h, int option, int64_t value) {
         if (value < 0 || value > 64) return LP_E_INVALID;
         h->chunk_lines = (uint32_t)value;
         return LP_OK;
-    case LP_OPT_ONE_PASS:
-        h->one_pass = value != 0;
-        return LP_OK;
+    case LP_OPT_ONE_PASS: return value == 1 ? LP_OK : LP_E_INVALID;  // (the only mode; 1 changes nothing)
     case LP_OPT_FIXED_SHAPE:
         h->fixed_shape = value != 0;
         return LP_OK;
@@ -926,7 +908,7 @@ int lp_counters(lp_handle* h, uint64_t* out, int n) {
     if (!h || !out) return LP_E_INVALID;
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
-    const uint64_t v[12] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_waves,
+    const uint64_t v[12] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_lines,
                             (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines,
                             h->uri_fix_lines, (uint64_t)h->last_launch.shape};
     for (int k = 0; k < n && k < 12; ++k) out[k] = v[k];

@@ -42,13 +42,12 @@ struct ParseLaunch {
     bool derived;           // ... some of them derived (type remapping: k_derived_lines after those)
     int n_uri, n_query;     // URI / query stages (the URI kernel instance)
     void* mid_event = nullptr;  // hipEvent_t recorded between the parse kernels and the URI kernels
-    bool chunked = false;       // one-format program: k_parse_chunks builds the line index itself
     uint32_t chunk_lines = 0;   // lines per byte chunk the chunked kernel aims for (0: default)
     int32_t chunk_wait = 0;     // polls for a chunk's line number before deferring it (0: default, < 0: none)
     bool lit_aware = true;      // the program has a [^\s]* / "$request" element a shorter end of which can meet
                                 // its literal (the chunked kernel's instance with literal-aware first candidates)
     bool simple = false;        // one format of the Apache common / combined family (capi simple_program)
-    bool multi = false;         // several LogFormats on the one-pass path (routing inside the chunk kernel)
+    bool multi = false;         // several LogFormats (match words in the chunk kernel, then the routing scan)
     int shape = 0;              // the fixed shape whose chunk kernel instance parses the program (lp_fixed.h
                                 // fixed_shape_of; FS_NONE: the instances per program class)
 };
@@ -56,20 +55,19 @@ struct ParseLaunch {
 // each), an LDS window of win_cap bytes (the chunk, 64 bytes before it, the
 // tail of its last line), n_chunks chunks.
 struct ChunkPlan {
-    uint32_t cb, win_cap, stk_words, chunk_stk;  // stk_words: the queued lines' kernels; chunk_stk: the chunk kernels'
+    uint32_t cb, win_cap, stk_words;  // stk_words: the DFS stack of the queued lines' kernels (the chunk kernels have none)
     int waves_per_cu;
     size_t lds;
     int64_t n_chunks;
 };
 ChunkPlan chunk_plan(const ParseLaunch& a);
-// parse every line, then the URI stages (k_uri_lines, and its direct path),
-// then meta->counters[0..4] += lines, ok, bad, fallback, arena bytes written.
-// Chunked (a.chunked): k_parse_chunks writes the line index, meta->n_lines /
-// cap_ovf and the lines' rows, k_parse_ovf_lines the lines it queued
+// parse every line of a device program, then the URI stages (k_uri_lines, and
+// its direct path), then meta->counters[0..4] += lines, ok, bad, fallback,
+// arena bytes written.  k_parse_chunks writes the line index, meta->n_lines /
+// cap_ovf and the lines' rows, k_parse_ovf_lines the lines it queued; with
+// several LogFormats k_route_ovf and the routing scan run between the two
 // (C.chunk_state zeroed, C.chunk_counts and C.deferred_chunks: chunk_plan().n_chunks records,
-// C.ovf_lines: cap_lines entries).  Otherwise the line index exists and the
-// staged waves, then the waves whose window did not fit LDS, run
-// (C.ovf_list and C.uri_ovf_list: parse_waves(cap_lines) + 1 entries each).
+// C.ovf_lines: cap_lines + 1 entries, C.uri_ovf_list: parse_waves(cap_lines) + 1).
 // C: the host copy of the columns the device holds.
 int launch_parse(const ParseLaunch& a, const DeviceArgs* d_args, const Columns& C, hipStream_t s);
 // k_parse_chunks of the fixed shape a.shape on `grid` blocks (parse_fixed.hip); -1: no such instance
@@ -88,9 +86,8 @@ int prof_clear_parse_fixed();
 int prof_read_uri(unsigned long long* out);
 int prof_clear_uri();
 #endif
-// sticky routing pass 1: C.fmt_match of every line
-int launch_route_match(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s);
-// sticky routing pass 2: C.fmt_match -> C.fmt_id (C.fmt_chunk: fmt_chunks()+1 words, the
+// the sticky routing scan: C.fmt_match (every line's match word, written by
+// the parse kernels) -> C.fmt_id (C.fmt_chunk: fmt_chunks()+1 words, the
 // state after the last line at [fmt_chunks(n_lines)])
 constexpr int FMT_CHUNK = 4096;
 __host__ __device__ inline int64_t fmt_chunks(int64_t n_lines) { return (n_lines + FMT_CHUNK - 1) / FMT_CHUNK; }

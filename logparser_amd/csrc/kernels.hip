@@ -1,6 +1,7 @@
 // gfx950 kernels of the logparser_amd engine: the separate line index (the
-// first batch of a handle, and multi-format programs, whose routing pass
-// needs the index first), the counter reduction, the sticky active-format
+// line count that sizes a handle's first batch, and programs that are not on
+// the device: a device program's parse kernel finds the lines itself), the
+// counter reduction, the sticky active-format
 // scan and the run histograms.  The parse kernels are parse.hip, the URI
 // kernels uri.hip; the shared wave scaffolding is kernels_common.h and the
 // per-line logic lp_device.h.
@@ -11,7 +12,7 @@
 //                     count, line_off[0] and the end sentinel, written on the device
 //   k_line_offsets    line start offsets from the bit masks (Hadoop LineRecordReader '\n' semantics)
 //   k_reduce_counts   per-wave status counts -> the batch counters
-//   k_fmt_*           the sticky active-format scan (routing pass 2)
+//   k_fmt_*           the sticky active-format scan over the lines' match words
 //   k_histograms      run histograms of a parsed batch (on demand)
 #include "kernels_common.h"
 

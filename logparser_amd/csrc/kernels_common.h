@@ -2,7 +2,7 @@
 // (kernels.hip: line index / counters / routing scan / histograms;
 // parse.hip: the parse kernels; uri.hip: the URI kernels).  The per-line
 // logic is lp_device.h; this header only holds the wave-level pieces around
-// it (line windows, staging, terminator masks, per-wave counts).
+// it (line windows, terminator masks, per-wave counts).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +87,9 @@ struct WaveStack {  // per-lane DFS stack, lane-interleaved (conflict-free)
     uint32_t* base;
     __device__ uint32_t& operator[](int k) const { return base[k * PW]; }
 };
+// The stack of a kernel that runs no DFS (the chunk kernels): it has no
+// storage, and any access from such an instance fails to compile.
+struct NoStack {};
 
 // The line of lane `own` of this wave (for work on another lane's line).
 template <typename LN>
@@ -133,55 +136,6 @@ __device__ __forceinline__ int crlf_len_hbm(const uint8_t* buf, const WaveLines&
     return W.active ? crlf_len(W.n, W.n > 0 ? buf[W.e - 1] : 0u) : W.n;
 }
 
-// Stage [w0, w1) into win (LDS) and the mask planes into msk16 (two 64-bit
-// planes per 64-byte block, as 16-bit pieces).  Returns whether every byte
-// but the terminators is TAB or printable ASCII (then no line needs the
-// guard scan of phase 1).
-__device__ __forceinline__ bool stage_window(const uint8_t* __restrict__ buf, uint64_t nbytes, uint64_t w0, uint64_t w1,
-                                             uint8_t* win, uint16_t* msk16) {
-    const int lane = lane_id();
-    const int nv = (int)((w1 - w0 + 15) >> 4);
-    const int nv4 = (nv + 3) & ~3;  // whole 64-byte mask blocks
-    uint32_t bad = 0;  // guard-failing bytes other than '\n' anywhere in the window
-    // SB loads in flight per lane before the first LDS store (one HBM
-    // round trip per SB x 1 KiB of window instead of one per 1 KiB)
-    constexpr int SB = 20;
-    const uint64_t full_end = nbytes & ~15ull;  // 16-byte pieces wholly inside the buffer
-    for (int k0 = lane; k0 < nv4; k0 += SB * PW) {
-        u32x4 v[SB];
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            const int k = k0 + j * PW;
-            const uint64_t p = w0 + 16ull * k;
-            v[j] = u32x4{0, 0, 0, 0};
-            if (k < nv && p + 16 <= full_end) v[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(buf + p));
-        }
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            const int k = k0 + j * PW;
-            if (k >= nv4) continue;
-            const uint64_t p = w0 + 16ull * k;
-            if (k < nv && p + 16 > full_end) {  // the buffer's last partial piece
-                auto word = [&](uint64_t q) {
-                    uint32_t w = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) w |= q + b < nbytes ? (uint32_t)buf[q + b] << (8 * b) : 0u;
-                    return w;
-                };
-                v[j] = u32x4{word(p), word(p + 4), word(p + 8), word(p + 12)};
-            }
-            *reinterpret_cast<u32x4*>(win + 16 * k) = v[j];
-            uint32_t m0, m1, g = 0, lf, other, cr;
-            bcls::classify16p(v[j][0], v[j][1], v[j][2], v[j][3], m0, m1, g, lf, other);
-            if (other) bcls::classify16c(v[j][0], v[j][1], v[j][2], v[j][3], g, cr);  // TAB, '\r', other controls
-            if (k < nv) bad |= g;
-            msk16[8 * (k >> 2) + (k & 3)] = (uint16_t)m0;
-            msk16[8 * (k >> 2) + 4 + (k & 3)] = (uint16_t)m1;
-        }
-    }
-    return !__any(bad != 0);
-}
-
 // Status counts of a wave's lines (lines, ok, bad, arena bytes written).
 struct WaveCounts {
     uint32_t act = 0, ok = 0, bad = 0, written = 0;
@@ -206,13 +160,13 @@ struct WaveCounts {
 
 // Phase 1 of one wave's lines (match, tokens, time, first line) and their
 // rows; adds the lines' counts to WC.  The URI stages run in k_uri_lines.
-template <bool MULTI, typename LN>
+template <typename LN>
 __device__ __forceinline__ void parse_wave(const Program& P, const Elem* elems, const Columns& C, const LN& L,
                                            bool active, int64_t li, WaveStack stk, bool clean, WaveCounts& WC) {
     LineOut o;
     o.status = ST_OK;
     LP_PROF(1);
-    if (active) phase1<MULTI>(P, elems, L, o, stk, C, li, clean, P.n_fmt > 1 ? (int)C.fmt_id[li] : 0);
+    if (active) phase1(P, elems, L, o, stk, C, li, clean, P.n_fmt > 1 ? (int)C.fmt_id[li] : 0);
     LP_PROF(9);
     if (active) write_line(P, o, C, li);
     if (active && !P.has_phase2()) C.arena_base[li] = 0;  // no URI kernel: an empty region for every line

@@ -2036,11 +2036,7 @@ __host__ __device__ LP_INLINE int parse_strf_time(const TimeStage& T, const LN& 
     bool zone_utc = false;
     int pos = a;
     auto low = [](uint32_t c) { return c | 0x20u; };  // safe fold against lower-case ASCII letters
-#if defined(LP_NO_STRF_FIXED)
-    const int fx = -1;
-#else
     const int fx = strf_fixed(T, L, a, b, fv, has);
-#endif
     LP_PROF(14);
     if (fx == ST_BAD) return ST_BAD;
     if (fx == ST_OK) pos = b;
@@ -2854,7 +2850,7 @@ __host__ __device__ LP_INLINE void fixed_fl_stages(const LN& L, LineOut& o, std:
 // (cand_first) in the first leaf; a kernel instance without them serves the
 // programs that have no such element (the code would reshape every
 // program's register allocation).
-// MULTI: a kernel of several-format programs (k_parse_lines): the lanes of
+// MULTI: the chunk kernel's instance for several-format programs: the lanes of
 // a wave hold lines of different LogFormats, so the stages run by slot (the
 // k-th time / first-line stage of each lane's own format together) and the
 // first leaf is walked per lane.

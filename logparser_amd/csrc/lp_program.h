@@ -359,7 +359,6 @@ struct Meta {
     unsigned long long counters[8];  // lines, ok, bad, fallback, arena bytes written, URI source bytes read
     unsigned long long n_lines;      // lines of the batch (the line index's count)
     unsigned long long cap_ovf;      // 1: more lines than the columns hold (nothing parsed, retry)
-    unsigned long long ovf_waves;    // waves queued for the direct (HBM) parse kernel
     unsigned long long arena_ovf;    // lines whose arena allocation did not fit its shard (retry)
     unsigned long long fmt_state;    // routed LogFormat after the batch's last line
     unsigned long long uri_ovf_waves;// waves whose URI bytes exceed the URI kernel's compact buffer (direct path)
@@ -369,7 +368,7 @@ struct Meta {
     // lines): how many failed, and the first failure (kind, then four values;
     // see check_fail in parse.hip).  Non-zero fails the batch (LP_E_DEVICE).
     unsigned long long err;
-    unsigned long long err_info[13];  // (with uri_fix_lines and dfs_lines it keeps shard_top on its own 128-B lines)
+    unsigned long long err_info[14];  // (13 used; with uri_fix_lines and dfs_lines it keeps shard_top on its own 128-B lines)
     unsigned long long uri_fix_lines;// lines whose URI needs uri_repair: low half, those k_uri_lines queued; high half, k_uri_overflow's own
     unsigned long long dfs_lines;    // lines the chunk kernel queued because the first leaf did not decide them (ST_REDO)
     unsigned long long shard_top[ARENA_SHARDS * 16];  // bump pointer of shard s at [16 s] (own 128-B line)
@@ -413,12 +412,10 @@ struct Columns {
     LP_G uint8_t* arena;
     uint64_t shard_cap;                  // arena bytes per shard (ARENA_SHARDS shards)
     LP_G Meta* meta;
-    LP_G uint32_t* ovf_list;             // waves for the direct parse kernel
     LP_G uint32_t* uri_ovf_list;         // waves for the direct URI kernel
     LP_G uint32_t* uri_fix_list;         // [cap_lines] lines k_uri_lines queued for uri_redo_line (low half of Meta::uri_fix_lines)
     LP_G uint32_t* wave_counts;          // [n_waves][WC_WORDS] lines ok bad fallback written (reduced after the launch)
-    // chunked parse (one-format programs: the line index built inside the
-    // parse kernel): per byte chunk the decoupled look-back word, its status
+    // chunked parse (the line index built inside the parse kernel): per byte chunk the decoupled look-back word, its status
     // counts, and the lines queued for the direct kernel
     LP_G uint64_t* chunk_state;          // [n_chunks] aggregate / inclusive line counts
     LP_G uint32_t* chunk_counts;         // [n_chunks][WC_WORDS]

@@ -78,7 +78,8 @@ struct ChunkScan {
 };
 
 // Stage the window [w0, w1) (w0 64-byte aligned) into LDS with its mask
-// planes, as stage_window, and find the chunk's line starts: every
+// planes (two 64-bit planes per 64-byte block, as 16-bit pieces) and find
+// the chunk's line starts: every
 // terminator t in [t_lo, t_hi) starts a line at t + 1, numbered in order
 // from `first` (1 when the chunk also holds the line starting at byte 0).
 // starts[r] = window offset of the r-th start (r < MAXS).
@@ -334,8 +335,10 @@ __device__ __noinline__ void chunk_excess(const uint8_t* __restrict__ buf, uint6
 
 // Chunk c of cb bytes on one wave: stage its window, publish its line count,
 // phase 1 of its lines, then (its first line number known) the line index
-// entries and rows.  LDS: [elements][DFS stack][starts][window (win_cap)]
-// [mask planes (win_cap / 4)].  direct: every line goes to the direct kernel
+// entries and rows.  LDS: [elements][starts][window (win_cap)]
+// [mask planes (win_cap / 4)].  No DFS runs here (a line that needs it is
+// queued), so the matchers get a stack without storage (NoStack).
+// direct: every line goes to the direct kernel
 // (LP_OPT_FORCE_DIRECT, tests).
 // second: the deferred pass (the chunk's count is published and the scanner
 // has finished: the line number is read, not waited for).
@@ -352,14 +355,14 @@ __device__ __noinline__ void chunk_excess(const uint8_t* __restrict__ buf, uint6
 template <bool LA, bool SIMPLE, bool MF = false, int SHAPE = FS_NONE>
 __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uint64_t nbytes, const Program& P,
                                             const Columns& C, const Elem* s_elems, uint8_t* smem, int64_t c,
-                                            int64_t n_chunks, uint32_t cb, uint32_t win_cap, uint32_t stk_words,
-                                            int direct, int wait_max, bool second) {
+                                            int64_t n_chunks, uint32_t cb, uint32_t win_cap, int direct,
+                                            int wait_max, bool second) {
     const uint64_t c0 = (uint64_t)c * cb;
     const uint64_t c1 = c0 + cb < nbytes ? c0 + cb : nbytes;
     const int lane = lane_id();
-    WaveStack stk{reinterpret_cast<uint32_t*>(smem + 16 * P.n_elems) + lane};
-    uint32_t* starts = reinterpret_cast<uint32_t*>(smem + 16 * P.n_elems + 4 * stk_words);
-    uint8_t* win = smem + 16 * P.n_elems + 4 * stk_words + 16 * ((4 * MAXS + 15) / 16);
+    const NoStack stk;
+    uint32_t* starts = reinterpret_cast<uint32_t*>(smem + 16 * P.n_elems);
+    uint8_t* win = smem + 16 * P.n_elems + 16 * ((4 * MAXS + 15) / 16);
     uint16_t* msk16 = reinterpret_cast<uint16_t*>(win + win_cap);
     // window: 64 bytes before the chunk (its first start needs the byte
     // before it), the chunk, then the tail of its last line
@@ -411,11 +414,7 @@ __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uin
             else phase1<true, LA, false, false, true>(P, s_elems, L, o, stk, C, 0, S.clean, __builtin_ctz(mm));
         }
     } else {
-#if defined(LP_DFS_IN_CHUNKS)  // (experiment builds: the backtracking DFS inside the chunk kernel, as before round 6)
-        if (lds_line) phase1<false, LA, SIMPLE, true>(P, s_elems, L, o, stk, C, 0, S.clean, 0);
-#else
         if (lds_line) phase1<false, LA, SIMPLE, false, false, SHAPE>(P, s_elems, L, o, stk, C, 0, S.clean, 0);  // (no DFS: ST_REDO)
-#endif
     }
     LP_PROF(9);
     const uint64_t base = chunk_base(C.chunk_state, c, S.count, second ? (int)CHUNK_WAIT_MAX : wait_max);
@@ -476,7 +475,7 @@ __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uin
 template <bool LA, bool SIMPLE, bool MF, int SHAPE = FS_NONE>
 __global__ __launch_bounds__(PW, MF ? LP_MF_WPE : 2) void k_parse_chunks(const uint8_t* __restrict__ buf, uint64_t nbytes,
                                                      const DeviceArgs* __restrict__ args, uint32_t cb, uint32_t win_cap,
-                                                     uint32_t stk_words, int direct, int wait_max) {
+                                                     int direct, int wait_max) {
     const Program& P = args->prog;
     const Columns& C = args->cols;
     const int64_t n_chunks = (int64_t)((nbytes + cb - 1) / cb);
@@ -489,8 +488,8 @@ __global__ __launch_bounds__(PW, MF ? LP_MF_WPE : 2) void k_parse_chunks(const u
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     Elem* s_elems = reinterpret_cast<Elem*>(smem);
     load_elems(P, s_elems);
-    parse_chunk<LA, SIMPLE, MF, SHAPE>(buf, nbytes, P, C, s_elems, smem, c, n_chunks, cb, win_cap, stk_words, direct,
-                                       wait_max, false);
+    parse_chunk<LA, SIMPLE, MF, SHAPE>(buf, nbytes, P, C, s_elems, smem, c, n_chunks, cb, win_cap, direct, wait_max,
+                                       false);
 }
 
 // The deferred pass: the chunks in C.deferred_chunks (none in a normal
@@ -499,7 +498,7 @@ __global__ __launch_bounds__(PW, MF ? LP_MF_WPE : 2) void k_parse_chunks(const u
 template <bool LA, bool SIMPLE, bool MF>
 __global__ __launch_bounds__(PW, 2) void k_parse_deferred(const uint8_t* __restrict__ buf, uint64_t nbytes,
                                                        const DeviceArgs* __restrict__ args, uint32_t cb,
-                                                       uint32_t win_cap, uint32_t stk_words, int direct) {
+                                                       uint32_t win_cap, int direct) {
     const Program& P = args->prog;
     const Columns& C = args->cols;
     const uint64_t nd = C.meta->deferred;
@@ -510,7 +509,7 @@ __global__ __launch_bounds__(PW, 2) void k_parse_deferred(const uint8_t* __restr
     load_elems(P, s_elems);
     for (uint64_t q = blockIdx.x; q < nd; q += gridDim.x) {
         parse_chunk<LA, SIMPLE, MF>(buf, nbytes, P, C, s_elems, smem, (int64_t)C.deferred_chunks[q], n_chunks, cb,
-                                    win_cap, stk_words, direct, 0, true);
+                                    win_cap, direct, 0, true);
         __syncthreads();  // this chunk's LDS reads are done before the next one is staged
     }
 }

@@ -13,7 +13,7 @@ namespace {
 template <int SHAPE>
 void run_fixed(const ParseLaunch& a, const DeviceArgs* d_args, const ChunkPlan& cp, unsigned grid, hipStream_t s) {
     hipLaunchKernelGGL((k_parse_chunks<false, true, false, SHAPE>), dim3(grid), dim3(PW), cp.lds, s, a.buf, a.nbytes,
-                       d_args, cp.cb, cp.win_cap, cp.chunk_stk, a.force_direct ? 1 : 0, a.chunk_wait);
+                       d_args, cp.cb, cp.win_cap, a.force_direct ? 1 : 0, a.chunk_wait);
 }
 }  // namespace
 

@@ -11,7 +11,7 @@ namespace {
 
 // ------------------------------------------------------------------ URIs
 // The URI and query-string stages of a wave's 64 lines (HttpUriDissector,
-// QueryStringFieldDissector), after k_parse_lines wrote the lines' status and
+// QueryStringFieldDissector), after the parse kernels wrote the lines' status and
 // spans.  Each lane's URI sources (request URI, referer, ...) are gathered
 // from the input into a compact LDS buffer (only the URI bytes: a few KiB per
 // wave, so many waves share a CU and hide the arena atomics and the query
@@ -152,13 +152,11 @@ __device__ __forceinline__ UriLane<NU> uri_lane(const Program& P, const Columns&
 // state: resume, fa, first_pct, rewr bit 1, the query table (slots, count,
 // s, lp).  L: the lane's line view (compact buffer with its UEV plane);
 // A.p / A.used: the line's region and where its table starts.
-// SLOT: u differs between lanes (the k-th URI stage of each lane's own
-// LogFormat, -1 none): an event takes its owner line's table flag.
-template <bool SLOT, typename CL>
+template <typename CL>
 __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL& L, bool part, int a, int b,
                                               uint32_t usep, const Arena& A, uint64_t* heads, UriWalk& Wk) {
     const int lane = lane_id();
-    const bool table = u >= 0 && P.uri[u].want_query && P.uri[u].query_stage >= 0;  // uniform unless SLOT
+    const bool table = P.uri[u].want_query && P.uri[u].query_stage >= 0;  // (wave-uniform)
     const uint32_t cnt = part ? usep : 0u;
     const uint32_t x = wave_incl_scan_dpp(cnt);
     const uint32_t eb = x - cnt, E = lane_value(x, 63);
@@ -217,8 +215,7 @@ __device__ __forceinline__ void uri_walk_coop(const Program& P, int u, const CL&
         const int qfa = __shfl(q, mfa ? lsb64(mfa) : lane);
         const int fa_j = cfa >= 0 ? cfa : (mfa ? qfa : -1);  // the first '&' / '?' before me
         const bool pp = live && ((pct && !bad_pct) || c == '+');
-        const bool otable = SLOT ? __shfl((int)table, ow) != 0 : table;  // the owner line's stage has a table
-        const bool isB = otable && live && aq && fa_j >= 0;  // a piece boundary after fa
+        const bool isB = table && live && aq && fa_j >= 0;  // a piece boundary after fa
         const uint64_t BB = __ballot(isB), BPP = __ballot(pp);
         const uint64_t mB = BB & seg_lt, mP = BPP & seg_lt;
         const int qpb = __shfl(q, mB ? msb64(mB) : lane), qpp = __shfl(q, mP ? msb64(mP) : lane);
@@ -339,9 +336,6 @@ struct QDescs {
 // Phase 2, the arena allocation and the query pieces of one wave; lu(u) is
 // the lane's line view of URI stage u (valid for every lane, empty stages
 // included: the query pass reads other lanes' views).
-// SLOT (several LogFormats): pass k runs, on every lane, the k-th URI stage of
-// the lane's own LogFormat (URI stages by slot: the lanes of all formats
-// walk together instead of each format's stages under a partial mask).
 // A line whose URI the reference repairs (ST_REPAIR) is stored as FALLBACK;
 // QUEUE: it is appended to uri_fix_list (k_uri_lines), else `redo` tells the
 // caller to redo it (k_uri_overflow, which also works the list off).
@@ -350,7 +344,7 @@ struct QDescs {
 // LP_PROF(21) calls a view's mask(): query_prep, query_name and
 // url_decode_value read bytes and words only), and the direct path never
 // reads it.
-template <int NU, int NQ, bool COOP, bool SLOT, bool QUEUE, typename LU, typename LL>
+template <int NU, int NQ, bool COOP, bool QUEUE, typename LU, typename LL>
 __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, UriLane<NU>& U, LU&& lu, LL&& ll,
                                          bool active, int64_t li, int64_t wave, uint64_t* heads, uint64_t* scratch,
                                          WaveCounts& WC, bool& redo) {
@@ -419,18 +413,8 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
     // phase 2 (lp_device.h phase2), stage by stage for the whole wave: the
     // compact path walks the stages' event bytes cooperatively
     const int nu = P.n_uri < NU ? P.n_uri : NU;
-    for (int sl = 0; sl < nu; ++sl) {
-        int u = sl;  // this lane's stage of the pass
-        if constexpr (SLOT) {
-            u = -1;
-            for (int v = 0, c = 0; v < nu; ++v)
-                if (P.uri[v].fmt == U.fmt) {
-                    if (c == sl) u = v;
-                    ++c;
-                }
-            if (!__any(u >= 0)) break;  // no lane's LogFormat has a sl-th stage
-        }
-        const bool fmt_ok = live && o.status == ST_OK && u >= 0 && P.uri[u].fmt == U.fmt;
+    for (int u = 0; u < nu; ++u) {
+        const bool fmt_ok = live && o.status == ST_OK && P.uri[u].fmt == U.fmt;
         const uint32_t sp = U.sp.get(u);
         const int a = (int)(sp & 0xFFFF), b = (int)(sp >> 16);
         const bool part = fmt_ok && b > a;
@@ -438,12 +422,12 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
             C.u_flags[u][li] = 0;
             if (P.uri[u].query_stage >= 0) { C.q_count[P.uri[u].query_stage][li] = 0; C.q_params[P.uri[u].query_stage][li] = 0; }
         }
-        LP_PROF(10 + 2 * sl);
+        LP_PROF(10 + 2 * u);
         UriWalk Wk;
         if constexpr (COOP) {
-            LP_PROF(50 + 4 * sl);
-            uri_walk_coop<SLOT>(P, u, lu(u), part, a, b, U.usep.get(u), A, heads, Wk);
-            LP_PROF(51 + 4 * sl);
+            LP_PROF(50 + 4 * u);
+            uri_walk_coop(P, u, lu(u), part, a, b, U.usep.get(u), A, heads, Wk);
+            LP_PROF(51 + 4 * u);
         } else if (part) {
             uri_walk_fast(P, u, lu(u), a, b, U.usep.get(u), A, Wk);
         }
@@ -451,7 +435,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
             const int st = uri_stage_rest<UR_OFF>(P, u, lu(u), a, b, U.usep.get(u), A, C, li, o, Wk);
             if (st != ST_OK) o.status = st;  // (ST_REPAIR too: settled where the status is stored)
         }
-        LP_PROF(11 + 2 * sl);
+        LP_PROF(11 + 2 * u);
     }
     if (live && lend && o.status == ST_OK) {
         bool filled = true;
@@ -660,7 +644,7 @@ __device__ __forceinline__ void uri_wave(const Program& P, const Columns& C, Uri
 // The URI stages of one wave on the compact path: its lines' URI bytes
 // gathered into cbuf (CAP bytes) with their UEV plane, then uri_wave.
 // Returns false, having done nothing, when the wave's bytes exceed CAP.
-template <int NU, int NQ, bool SLOT, uint32_t CAP>
+template <int NU, int NQ, uint32_t CAP>
 __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uint64_t nbytes, const Program& P,
                                             const Columns& C, int64_t wave, int64_t n_lines, uint32_t* cbuf,
                                             uint64_t* plane, uint64_t* heads, WaveCounts& WC, bool& redo) {
@@ -783,17 +767,14 @@ __device__ __forceinline__ bool uri_compact(const uint8_t* __restrict__ buf, uin
         if (lin) f(LineT<lds_bytes>{(lds_bytes)cbuf, lorig, lend});
         else f(LineT<const LP_G uint8_t*>{lsp - lmis, lmis, lend});
     };
-    uri_wave<NU, NQ, true, SLOT, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, heads, plane, WC, redo);
+    uri_wave<NU, NQ, true, CAP == URI_CAP>(P, C, U, lu, ll, active, li, wave, heads, plane, WC, redo);
     return true;
 }
 
 // 16 waves per CU: the LDS share allows them, and __launch_bounds__(64, 4)
 // (4 waves per SIMD) keeps the registers within 128
-#ifndef LP_URI_SLOT_WPE
-#define LP_URI_SLOT_WPE 4  // waves per SIMD of the several-format (SLOT) instance
-#endif
-template <int NU, int NQ, bool SLOT>
-__global__ __launch_bounds__(PW, SLOT ? LP_URI_SLOT_WPE : 4) void k_uri_lines(const uint8_t* __restrict__ buf, uint64_t nbytes,
+template <int NU, int NQ>
+__global__ __launch_bounds__(PW, 4) void k_uri_lines(const uint8_t* __restrict__ buf, uint64_t nbytes,
                                                      const DeviceArgs* __restrict__ args) {
     const Program& P = args->prog;
     const Columns& C = args->cols;
@@ -807,7 +788,7 @@ __global__ __launch_bounds__(PW, SLOT ? LP_URI_SLOT_WPE : 4) void k_uri_lines(co
     __shared__ uint64_t heads[OWNER_LDS_WORDS];  // (with cbuf and plane within 10,240 B: 16 workgroups per CU)
     WaveCounts WC;
     bool redo;  // (unused: this kernel queues such lines)
-    if (uri_compact<NU, NQ, SLOT, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) WC.store(C, wave);
+    if (uri_compact<NU, NQ, URI_CAP>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) WC.store(C, wave);
     else if (lane_id() == 0) C.uri_ovf_list[atomicAdd(&C.meta->uri_ovf_waves, 1ull)] = (uint32_t)wave;
 }
 
@@ -893,7 +874,7 @@ __device__ __forceinline__ void uri_redo_line(const uint8_t* __restrict__ buf, u
 // Meta::uri_fix_lines (the lower half is the list's length, read by every
 // block here).
 constexpr uint32_t URI_CAP_OVF = 4 * URI_CAP;
-template <int NU, int NQ, bool SLOT>
+template <int NU, int NQ>
 __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__ buf, uint64_t nbytes,
                                                      const DeviceArgs* __restrict__ args) {
     const Program& P = args->prog;
@@ -909,7 +890,7 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
         const int64_t wave = C.uri_ovf_list[q];
         WaveCounts WC;
         bool redo = false;
-        if (!uri_compact<NU, NQ, SLOT, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) {
+        if (!uri_compact<NU, NQ, URI_CAP_OVF>(buf, nbytes, P, C, wave, n_lines, cbuf, plane, heads, WC, redo)) {
             const WaveLines W = wave_lines(C, wave, n_lines, nbytes);
             UriLane<NU> U = uri_lane<NU>(P, C, W.li, W.active);
             const LP_G uint8_t* ls = (const LP_G uint8_t*)(buf) + W.s;
@@ -917,7 +898,7 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
             const LineT<const LP_G uint8_t*> L{ls - mis, mis, crlf_len_hbm(buf, W)};
             auto lu = [&](int) { return L; };
             auto ll = [&](int lend, auto&& f) { f(LineT<const LP_G uint8_t*>{ls - mis, mis, lend}); };
-            uri_wave<NU, NQ, false, SLOT, false>(P, C, U, lu, ll, W.active, W.li, wave, heads, plane, WC, redo);
+            uri_wave<NU, NQ, false, false>(P, C, U, lu, ll, W.active, W.li, wave, heads, plane, WC, redo);
         }
         __syncthreads();
         WC.store(C, wave);
@@ -979,20 +960,14 @@ int launch_uri(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s) {
     const int64_t grid = waves < 1024 ? waves : 1024;
     // most programs have at most two URI and two query stages (the request
     // URI and the referer): an instance keeping two of each
-    // several LogFormats (not a.chunked): the instance running URI stages by slot
-    if (!a.chunked) {
-        hipLaunchKernelGGL((k_uri_lines<MAX_URI, MAX_QUERY, true>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf,
-                           a.nbytes, d_args);
-        hipLaunchKernelGGL((k_uri_overflow<MAX_URI, MAX_QUERY, true>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf,
-                           a.nbytes, d_args);
-    } else if (a.n_uri <= 2 && a.n_query <= 2) {
-        hipLaunchKernelGGL((k_uri_lines<2, 2, false>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
-        hipLaunchKernelGGL((k_uri_overflow<2, 2, false>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
+    if (a.n_uri <= 2 && a.n_query <= 2) {
+        hipLaunchKernelGGL((k_uri_lines<2, 2>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
+        hipLaunchKernelGGL((k_uri_overflow<2, 2>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
     } else {
-        hipLaunchKernelGGL((k_uri_lines<MAX_URI, MAX_QUERY, false>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf,
-                           a.nbytes, d_args);
-        hipLaunchKernelGGL((k_uri_overflow<MAX_URI, MAX_QUERY, false>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf,
-                           a.nbytes, d_args);
+        hipLaunchKernelGGL((k_uri_lines<MAX_URI, MAX_QUERY>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf, a.nbytes,
+                           d_args);
+        hipLaunchKernelGGL((k_uri_overflow<MAX_URI, MAX_QUERY>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf, a.nbytes,
+                           d_args);
     }
     if (a.derived) hipLaunchKernelGGL(k_derived_lines, dim3((unsigned)waves), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
     return hipGetLastError() == hipSuccess ? 0 : -1;

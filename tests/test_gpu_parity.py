@@ -332,18 +332,16 @@ def test_strftime_config3_gpu(oracle):
     assert s["bad"] > 300 and s["ok"] > 1000, s
 
 
-@pytest.mark.parametrize("one_pass", [1, 0])
-def test_mixed_formats_gpu(oracle, one_pass):
+def test_mixed_formats_gpu(oracle):
     """Sticky multi-format routing on the device against the stateful oracle
     on a mixed corpus (formats that are not mutually exclusive, mutated lines),
-    across routing chunks and across two batches of one handle: one pass
-    (routing inside the chunk kernel, the lines several formats match after
-    the scan) and the index / routing / parse passes (LP_OPT_ONE_PASS 0)."""
+    across routing chunks and across two batches of one handle (routing inside
+    the chunk kernel, the lines several formats match after the scan)."""
     from test_emu_parity import MIXED, mixed_lines, mutate
     fields = paths(oracle, MIXED)
     rng = random.Random(57)
     lines = [mutate(rng, l) if rng.random() < 0.05 else l for l in mixed_lines(30000, 58)]
-    p = lpa.HttpdLoglineParser(MIXED, fields, options={lpa.OPT_ONE_PASS: one_pass})
+    p = lpa.HttpdLoglineParser(MIXED, fields)
     o = oracle.Oracle(MIXED, fields)
     for part in (lines[:17000], lines[17000:]):
         r = p.parse_batch(b"".join(l + b"\n" for l in part))

@@ -213,18 +213,15 @@ def test_config4_ipv6_corpus_gpu(oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("one_pass", [1, 0])
-def test_mixed_handle_ipv6_gpu(oracle, one_pass):
+def test_mixed_handle_ipv6_gpu(oracle):
     """Test 6.  4,000 lines of the three-format corpus, IPv6 hosts on 30 % of
-    the NGINX ones, line by line against the sticky oracle: no FALLBACK; the
-    index / routing / parse passes (LP_OPT_ONE_PASS 0) give the same."""
+    the NGINX ones, line by line against the sticky oracle: no FALLBACK."""
     from test_gpu_parity import paths
     base = lpa.synth(lpa.SYNTH_MIXED, 20261021, 0, 4000).split(b"\n")[:-1]
     lines, v6 = ipv6_corpus(base, 62, only=lambda l: not l.endswith(b'"') and l[-1:] in (b"p", b"."))
     assert len(v6) > 250
     fields = paths(oracle, MIXED)
-    r = lpa.HttpdLoglineParser(MIXED, fields, options={lpa.OPT_ONE_PASS: one_pass}).parse_batch(
-        b"".join(l + b"\n" for l in lines))
+    r = lpa.HttpdLoglineParser(MIXED, fields).parse_batch(b"".join(l + b"\n" for l in lines))
     assert r.n_lines == 4000
 
     def want():

@@ -98,8 +98,7 @@ def test_long_defective_uris_gpu(oracle, direct):
     assert r.counters["ok"] == 192, r.counters
 
 
-@pytest.mark.parametrize("one_pass", [1, 0])
-def test_three_formats_gpu(oracle, one_pass):
+def test_three_formats_gpu(oracle):
     """The formats and corpus of test_mixed_formats_gpu, defects planted in
     request URIs of every format (the 'combined' and NGINX ones among them)."""
     from test_emu_parity import MIXED, mixed_lines
@@ -115,7 +114,7 @@ def test_three_formats_gpu(oracle, one_pass):
             planted.add(k)
         lines.append(l)
     assert len(planted) > 1000
-    p = lpa.HttpdLoglineParser(MIXED, fields, options={lpa.OPT_ONE_PASS: one_pass})
+    p = lpa.HttpdLoglineParser(MIXED, fields)
     r = p.parse_batch(b"".join(l + b"\n" for l in lines))
     o = oracle.Oracle(MIXED, fields)
     ok = 0

@@ -1,6 +1,6 @@
 """Run the LP_PROFILE build on synthetic config-2 lines and print the mean
 cycles per wave between consecutive instrumentation points of the parse kernel
-(k_parse_chunks, or k_parse_lines for several LogFormats) and k_uri_lines
+(k_parse_chunks, every instance) and k_uri_lines
 (per-wave timestamps, no atomics)."""
 import ctypes
 import os
@@ -79,7 +79,7 @@ for k, (nm, inside) in ACC.items():
         print("  %-18s %9.0f cycles/wave  (inside %s; %d waves, %d with a pass)"
               % (nm, T[rows, k].mean(), inside, int(rows.sum()), int((T[rows, k] != 0).sum())))
 
-# first-leaf match cycles per element (LP_PROF_EL, slots 64 + i), k_parse_lines waves
+# first-leaf match cycles per element (LP_PROF_EL, slots 64 + i), the parse kernel's waves
 el = T[:, 64:96]
 rows = T[:, 0] != 0
 if rows.any():
