@@ -66,6 +66,8 @@ def lib():
         L.emu_strf.restype = ctypes.c_int
         L.emu_strf.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.POINTER(ctypes.c_int64)]
+        L.emu_leaf_stats.restype = ctypes.c_int
+        L.emu_leaf_stats.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
         _lib = L
     return _lib
 
@@ -129,6 +131,14 @@ class Emu:
         out = (ctypes.c_int64 * 5)()
         n = lib().emu_strf(self.h, value, len(value), off, 1 if use_fixed else 0, out)
         return n, tuple(out)
+
+    def leaf_class(self, line):
+        """how a one-format program's phase 1 decides the line (emu_leaf_stats): "leaf" (the first DFS leaf
+        matches), "prefilter" (ruled out by the quote count or the line tail) or "dfs" (the backtracking DFS)"""
+        out = (ctypes.c_int64 * 4)()
+        rc = lib().emu_leaf_stats(self.h, line + b"\n", len(line) + 1, out)
+        assert rc == 0 and out[0] == 1 and out[1] + out[2] + out[3] == 1, (rc, list(out))
+        return "leaf" if out[1] else "prefilter" if out[2] else "dfs"
 
     def casts(self, target):
         c = lib().emu_casts(self.h, target.encode())
