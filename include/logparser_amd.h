@@ -96,6 +96,31 @@ typedef struct lp_remap {
 lp_handle *lp_compile_remapped(const char *logformats, const char *const *paths, int n_paths,
                                const lp_remap *remaps, int n_remaps, int device, int *status, char *err,
                                size_t errlen);
+
+/* Parser.addDissector(dissector) (core/Parser.java:154-160): a dissector of
+ * the reference's httpdlog-parser jar that is not registered by default, by
+ * class name as Hive's "load:" / Pig's "-load:" give it, with their settings
+ * string.  Known: "ScreenResolutionDissector" (also
+ * "nl.basjes.parse.httpdlog.dissectors.ScreenResolutionDissector"): a value
+ * remapped to SCREENRESOLUTION delivers SCREENWIDTH:<path>.width and
+ * SCREENHEIGHT:<path>.height.  The settings are accepted and kept, but the
+ * value is split on "x" whatever they say: the reference dissects with a
+ * fresh instance that never sees them.  Registering a class twice is the same
+ * as once; any other name is LP_E_INVALID.  settings may be NULL (""). */
+typedef struct lp_dissector {
+    const char *name;
+    const char *settings;
+} lp_dissector;
+/* lp_compile_remapped with registered dissectors (n_dissectors may be 0: the
+ * same call).  Remapped values that are re-dissected on the device -- a
+ * SCREENRESOLUTION (registered) or a MOD_UNIQUE_ID (ModUniqueIdDissector,
+ * registered by default) -- must be a captured token or a requested query
+ * parameter, at most 8 of them per program; a parameter that occurs twice on
+ * a line, and a SCREENRESOLUTION whose split lacks a requested part (the
+ * reference throws), make the line LP_LINE_FALLBACK. */
+lp_handle *lp_compile_dissectors(const char *logformats, const char *const *paths, int n_paths,
+                                 const lp_remap *remaps, int n_remaps, const lp_dissector *dissectors,
+                                 int n_dissectors, int device, int *status, char *err, size_t errlen);
 void lp_free(lp_handle *h);
 
 /* Parser.getPossiblePaths(max_depth) for a logformat: '\n'-separated, sorted.
@@ -105,6 +130,10 @@ int64_t lp_possible_paths(const char *logformats, int max_depth, char *out, size
  * dissectors produce below it (core/Parser.java:954-962). */
 int64_t lp_possible_paths_remapped(const char *logformats, int max_depth, const lp_remap *remaps, int n_remaps,
                                    char *out, size_t cap);
+/* The same with registered dissectors: a path remapped to SCREENRESOLUTION
+ * lists its .width / .height below it.  LP_E_INVALID for an unknown class. */
+int64_t lp_possible_paths_dissectors(const char *logformats, int max_depth, const lp_remap *remaps, int n_remaps,
+                                     const lp_dissector *dissectors, int n_dissectors, char *out, size_t cap);
 
 /* Options (lp_set_option). */
 #define LP_OPT_FORCE_DIRECT 1  /* 1: every wave reads its lines from HBM (no LDS window);
@@ -364,8 +393,12 @@ int lp_casts(lp_handle *h, const char *target);
  * the call returns once they are filled.  Request cookies, raw-token query
  * strings, Set-Cookie cookies and their value / expires / domain / comment /
  * path attributes, upstream list items (N.value / N.redirected, SECOND_MILLIS
- * in ms and us), BinaryIP and the first line / URI / query values are device
- * columns.  LP_E_UNSUPPORTED names a path whose value only the host replay
+ * in ms and us), BinaryIP, the first line / URI / query values, and the
+ * outputs of the dissectors on a remapped token or query parameter
+ * (SCREENWIDTH:<p>.width / SCREENHEIGHT:<p>.height of a SCREENRESOLUTION;
+ * TIME.EPOCH:<p>.epoch, IP:<p>.ip, PROCESSID:<p>.processid, COUNTER:<p>.counter,
+ * THREAD_INDEX:<p>.threadindex of a MOD_UNIQUE_ID) are device columns.
+ * LP_E_UNSUPPORTED names a path whose value only the host replay
  * derives (a converter applied to an already converted value) or a DOUBLE
  * column of a string-valued path (Double.parseDouble): build those from a
  * host copy. */

@@ -251,6 +251,14 @@ def lib():
     L.lp_possible_paths_remapped.restype = ctypes.c_int64
     L.lp_possible_paths_remapped.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(LpRemap), ctypes.c_int,
                                              ctypes.c_char_p, ctypes.c_size_t]
+    L.lp_compile_dissectors.restype = ctypes.c_void_p
+    L.lp_compile_dissectors.argtypes = [ctypes.c_char_p, c_char_pp, ctypes.c_int, ctypes.POINTER(LpRemap), ctypes.c_int,
+                                        ctypes.POINTER(LpDissector), ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_size_t]
+    L.lp_possible_paths_dissectors.restype = ctypes.c_int64
+    L.lp_possible_paths_dissectors.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(LpRemap), ctypes.c_int,
+                                               ctypes.POINTER(LpDissector), ctypes.c_int, ctypes.c_char_p,
+                                               ctypes.c_size_t]
     L.lp_parse_batch.restype = ctypes.c_int
     L.lp_parse_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
     L.lp_parse_batch_at.restype = ctypes.c_int
@@ -340,13 +348,33 @@ def _remap_array(remaps):
     return arr, len(remaps)
 
 
-def get_possible_paths(logformat, max_depth=15, remaps=()):
+class LpDissector(ctypes.Structure):
+    """lp_dissector: Parser.addDissector of a registrable dissector, by class name, with its settings"""
+    _fields_ = [("name", ctypes.c_char_p), ("settings", ctypes.c_char_p)]
+
+
+def _dissector_array(dissectors):
+    """[(name, settings) or name] -> (lp_dissector array, count)"""
+    ds = [(d, "") if isinstance(d, str) else tuple(d) for d in dissectors]
+    arr = (LpDissector * max(1, len(ds)))()
+    for i, (n, st) in enumerate(ds):
+        arr[i] = LpDissector(n.encode(), (st or "").encode())
+    return arr, len(ds)
+
+
+def get_possible_paths(logformat, max_depth=15, remaps=(), dissectors=()):
     """Parser.getPossiblePaths(maxDepth) for a HttpdLoglineParser on logformat
-    (remaps: [(input, TYPE, casts)], its type remappings)."""
+    (remaps: [(input, TYPE, casts)], its type remappings; dissectors: [(class
+    name, settings) or class name], its added dissectors)."""
     cap = 1 << 20
     out = ctypes.create_string_buffer(cap)
     arr, n_rm = _remap_array(list(remaps))
-    n = lib().lp_possible_paths_remapped(logformat.encode(), max_depth, arr, n_rm, out, cap)
+    dz, n_dz = _dissector_array(list(dissectors))
+    n = lib().lp_possible_paths_dissectors(logformat.encode(), max_depth, arr, n_rm, dz, n_dz, out, cap)
+    if n == LP_E_INVALID:  # (cap > 0 and an empty list is length 0, never -1: the arguments were refused)
+        names = [bytes(dz[k].name).decode() for k in range(n_dz)]
+        raise InvalidDissectorException("unknown dissector class among %r" % names if names
+                                        else "lp_possible_paths_dissectors: invalid arguments")
     if n < 0:
         raise InvalidDissectorException("possible paths overflow")
     return [p for p in out.value.decode().split("\n") if p]
@@ -1076,6 +1104,7 @@ class HttpdLoglineParser:
         self._targets = {}       # cleaned "TYPE:path" -> [Target] (Parser.targets)
         self._remaps = {}        # path -> {TYPE} (Parser.typeRemappings)
         self._remap_casts = {}   # "TYPE:path" -> casts of a remapped target
+        self._dissectors = []    # (class name, settings) (Parser.addDissector)
         self._engine_fields = None
         self.device = device
         self.force_direct = force_direct
@@ -1108,6 +1137,18 @@ class HttpdLoglineParser:
         self._close()
         return self
 
+    # Parser.addDissector (core/Parser.java:154-160) of a dissector of the
+    # reference's httpdlog-parser jar that is not there by default
+    def add_dissector(self, name, settings=""):
+        """Register a dissector by class name (ScreenResolutionDissector, or
+        its fully qualified name as Hive's "load:" / Pig's "-load:" give it)
+        with its settings string.  The settings are kept but, as in the
+        reference, never reach the instance that dissects: a SCREENRESOLUTION
+        is always split on "x"."""
+        self._dissectors.append((name, settings or ""))
+        self._close()
+        return self
+
     def add_type_remappings(self, mappings):
         for name, types in mappings.items():
             for t in types:
@@ -1131,7 +1172,7 @@ class HttpdLoglineParser:
         return [(n, t, self._remap_casts[t + ":" + n]) for n in sorted(self._remaps) for t in sorted(self._remaps[n])]
 
     def get_possible_paths(self, max_depth=15):
-        return get_possible_paths(self.logformat, max_depth, self._remap_list())
+        return get_possible_paths(self.logformat, max_depth, self._remap_list(), self._dissectors)
 
     def _ensure(self):
         if self._h:
@@ -1145,8 +1186,9 @@ class HttpdLoglineParser:
         rm, n_rm = _remap_array(self._remap_list())
         st = ctypes.c_int(0)
         err = ctypes.create_string_buffer(1024)
-        h = L.lp_compile_remapped(self.logformat.encode(), arr, len(fields), rm, n_rm, self.device, ctypes.byref(st),
-                                  err, 1024)
+        dz, n_dz = _dissector_array(self._dissectors)
+        h = L.lp_compile_dissectors(self.logformat.encode(), arr, len(fields), rm, n_rm, dz, n_dz, self.device,
+                                    ctypes.byref(st), err, 1024)
         msg = err.value.decode(errors="replace")
         if not h:
             if st.value == LP_E_MISSING:

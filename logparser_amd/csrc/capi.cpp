@@ -462,6 +462,8 @@ int enqueue(lp_handle* h, bool sync_count) {
                            P.n_elems, P.max_stack, h->force_direct, P.has_phase2(), false, P.n_uri, P.n_query,
                            h->ev[4]};
         for (int u = 0; u < P.n_uri; ++u) pl.derived = pl.derived || P.uri[u].src_q >= 0;
+        // ... and the value stages that have a guard there (a parameter's occurrences, a SCREENRESOLUTION's parts)
+        for (int k = 0; k < P.n_val; ++k) pl.derived = pl.derived || P.val[k].src_q >= 0 || P.val[k].kind == lp::VK_SCREEN;
         if (!pl.mean_line && cap > 0) pl.mean_line = (nbytes + cap - 1) / (uint64_t)cap;
         pl.chunk_lines = h->chunk_lines;
         pl.chunk_wait = h->chunk_wait;
@@ -679,8 +681,22 @@ lp_handle* lp_compile(const char* logformats, const char* const* paths, int n_pa
 
 lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths, int n_paths, const lp_remap* remaps,
                                int n_remaps, int device, int* status, char* err, size_t errlen) {
+    return lp_compile_dissectors(logformats, paths, n_paths, remaps, n_remaps, nullptr, 0, device, status, err, errlen);
+}
+
+lp_handle* lp_compile_dissectors(const char* logformats, const char* const* paths, int n_paths, const lp_remap* remaps,
+                                 int n_remaps, const lp_dissector* dissectors, int n_dissectors, int device, int* status,
+                                 char* err, size_t errlen) {
     if (status) *status = LP_E_INVALID;
-    if (!logformats || (n_paths > 0 && !paths) || (n_remaps > 0 && !remaps)) { set_err(err, errlen, "null argument"); return nullptr; }
+    if (!logformats || (n_paths > 0 && !paths) || (n_remaps > 0 && !remaps) || (n_dissectors > 0 && !dissectors)) {
+        set_err(err, errlen, "null argument");
+        return nullptr;
+    }
+    std::vector<lp::AddDissector> dz;
+    for (int i = 0; i < n_dissectors; ++i) {
+        if (!dissectors[i].name) { set_err(err, errlen, "null dissector name"); return nullptr; }
+        dz.push_back(lp::AddDissector{dissectors[i].name, dissectors[i].settings ? dissectors[i].settings : ""});
+    }
     std::vector<lp::Remap> rm;
     for (int i = 0; i < n_remaps; ++i) {
         if (!remaps[i].input || !remaps[i].type) { set_err(err, errlen, "null remapping"); return nullptr; }
@@ -698,7 +714,7 @@ lp_handle* lp_compile_remapped(const char* logformats, const char* const* paths,
     std::vector<std::string> f;
     for (int i = 0; i < n_paths; ++i) f.emplace_back(paths[i]);
     std::string e;
-    int st = h->plan.build(logformats, f, e, rm);
+    int st = h->plan.build(logformats, f, e, rm, dz);
     if (st != LP_OK && st != LP_E_UNSUPPORTED) {
         if (status) *status = st;
         set_err(err, errlen, e);
@@ -736,7 +752,17 @@ int64_t lp_possible_paths(const char* logformats, int max_depth, char* out, size
 
 int64_t lp_possible_paths_remapped(const char* logformats, int max_depth, const lp_remap* remaps, int n_remaps,
                                    char* out, size_t cap) {
-    if (n_remaps > 0 && !remaps) return LP_E_INVALID;
+    return lp_possible_paths_dissectors(logformats, max_depth, remaps, n_remaps, nullptr, 0, out, cap);
+}
+
+int64_t lp_possible_paths_dissectors(const char* logformats, int max_depth, const lp_remap* remaps, int n_remaps,
+                                     const lp_dissector* dissectors, int n_dissectors, char* out, size_t cap) {
+    if ((n_remaps > 0 && !remaps) || (n_dissectors > 0 && !dissectors)) return LP_E_INVALID;
+    std::vector<lp::AddDissector> dz;
+    for (int i = 0; i < n_dissectors; ++i) {
+        if (!dissectors[i].name) return LP_E_INVALID;
+        dz.push_back(lp::AddDissector{dissectors[i].name, dissectors[i].settings ? dissectors[i].settings : ""});
+    }
     std::vector<lp::Remap> rm;
     for (int i = 0; i < n_remaps; ++i) {
         if (!remaps[i].input || !remaps[i].type) return LP_E_INVALID;
@@ -744,7 +770,7 @@ int64_t lp_possible_paths_remapped(const char* logformats, int max_depth, const 
     }
     std::vector<std::string> paths;
     std::string err;
-    lp::Plan::possible_paths(logformats ? logformats : "", max_depth, paths, err, rm);
+    if (lp::Plan::possible_paths(logformats ? logformats : "", max_depth, paths, err, rm, dz) != LP_OK) return LP_E_INVALID;
     std::string s;
     for (auto& p : paths) s += p + "\n";
     if (!out || s.size() + 1 > cap) return -(int64_t)(s.size() + 1);

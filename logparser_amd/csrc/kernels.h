@@ -39,7 +39,8 @@ struct ParseLaunch {
     int n_elems, stack_depth;
     bool force_direct;      // every wave on the direct (HBM) path: tests / diagnostics only
     bool uri;               // the program has URI stages (k_uri_lines after the parse kernel)
-    bool derived;           // ... some of them derived (type remapping: k_derived_lines after those)
+    bool derived;           // ... some of them derived (type remapping: k_derived_lines after those), or a value
+                            // stage has a guard there (then also without URI stages)
     int n_uri, n_query;     // URI / query stages (the URI kernel instance)
     void* mid_event = nullptr;  // hipEvent_t recorded between the parse kernels and the URI kernels
     uint32_t chunk_lines = 0;   // lines per byte chunk the chunked kernel aims for (0: default)

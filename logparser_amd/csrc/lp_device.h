@@ -19,6 +19,7 @@
 
 #include "lp_program.h"
 #include "lp_fixed.h"
+#include "lp_value.h"  // screen_split (the value stages' guard, derived_line)
 
 namespace lp {
 
@@ -3909,14 +3910,16 @@ __host__ __device__ LP_INLINE void query_pieces_serial(const Program& P, LQ&& lq
 // Returns 0 none (no such parameter, or an empty value: HttpUriDissector
 // does nothing for an empty input, HttpUriDissector.java:134-136), 1 found
 // (vref), 2 FALLBACK (two or more occurrences: each is dissected in turn).
+// (qparam_source: the same for parameter src_qname of query stage src_q --
+// a value stage's source too, lp_program.h ValStage)
 template <typename Cols>
-__host__ __device__ LP_INLINE int derived_source(const Program& P, const UriStage& U, const Cols& C, int64_t li,
-                                                 const LP_G uint8_t* line, const LP_G uint8_t* region, uint64_t& vref) {
-    const QueryStage& Q = P.query[U.src_q];
-    const uint32_t cnt = C.q_count[U.src_q][li];
+__host__ __device__ LP_INLINE int qparam_source(const Program& P, int src_q, int src_qname, const Cols& C, int64_t li,
+                                                const LP_G uint8_t* line, const LP_G uint8_t* region, uint64_t& vref) {
+    const QueryStage& Q = P.query[src_q];
+    const uint32_t cnt = C.q_count[src_q][li];
     if (cnt == 0) return 0;
-    const LP_G uint64_t* t = reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.q_params[U.src_q][li]));
-    const uint32_t no = Q.name_off[U.src_qname], nl = Q.name_len[U.src_qname];
+    const LP_G uint64_t* t = reinterpret_cast<const LP_G uint64_t*>(region + ref_off(C.q_params[src_q][li]));
+    const uint32_t no = Q.name_off[src_qname], nl = Q.name_len[src_qname];
     int found = 0;
     for (uint32_t k = 0; k < cnt; ++k) {
         const uint64_t nref = t[2 * k];
@@ -3929,6 +3932,11 @@ __host__ __device__ LP_INLINE int derived_source(const Program& P, const UriStag
         vref = t[2 * k + 1];
     }
     return found && ref_len(vref) > 0 ? 1 : 0;
+}
+template <typename Cols>
+__host__ __device__ LP_INLINE int derived_source(const Program& P, const UriStage& U, const Cols& C, int64_t li,
+                                                 const LP_G uint8_t* line, const LP_G uint8_t* region, uint64_t& vref) {
+    return qparam_source(P, U.src_q, U.src_qname, C, li, line, region, vref);
 }
 
 // Derived stage u on source [a, b) of L: the URI stage, then its query
@@ -4154,6 +4162,38 @@ __host__ __device__ LP_INLINE int derived_line(const Program& P, int fmt, const 
             st = derived_stage(P, u, L, (int)vo, (int)(vo + vl), R, C, li);
         }
         if (st != ST_OK) return st;
+    }
+    // The value stages' guard (lp_program.h ValStage), after the derived URI
+    // stages (a source may be a derived URI's parameter).  A parameter that
+    // occurs twice is FALLBACK, as for a derived URI (each occurrence is
+    // dissected in turn).  ScreenResolutionDissector reads parts[0] / parts[1]
+    // of split("x") for the requested outputs (ScreenResolutionDissector.java:
+    // 56-63): a missing part is an ArrayIndexOutOfBoundsException, no
+    // DissectionFailure -- the reference owns such a line.  ModUniqueIdDissector
+    // never throws: nothing to guard on a token.
+    for (int k = 0; k < P.n_val; ++k) {
+        const ValStage& S = P.val[k];
+        if (S.fmt != fmt) continue;
+        const LP_G uint8_t* vp;
+        uint32_t vl;
+        if (S.src_tok >= 0) {
+            if (S.kind != VK_SCREEN || ((C.tok_flags[li] >> S.src_tok) & 1u)) continue;
+            const uint32_t sp = C.tok_span[S.src_tok][li];
+            vp = lb + lo + (sp & 0xFFFFu);
+            vl = (sp >> 16) - (sp & 0xFFFFu);
+        } else {
+            uint64_t vref = 0;
+            const int f = qparam_source(P, S.src_q, S.src_qname, C, li, lb + lo, R.p, vref);
+            if (f == 2) return ST_FALLBACK;
+            if (f == 0 || S.kind != VK_SCREEN) continue;
+            vp = (ref_arena(vref) ? R.p : lb + lo) + ref_off(vref);
+            vl = ref_len(vref);
+        }
+        uint32_t wl, ho, hl;
+        const int parts = screen_split(vp, vl, wl, ho, hl);
+        // (the throw depends on what is requested; the planner makes a stage only below a requested output)
+        const int need = (S.want & VW_HEIGHT) ? 2 : (S.want & VW_WIDTH) ? 1 : 0;
+        if (parts >= 0 && parts < need) return ST_FALLBACK;
     }
     return ST_OK;
 }

@@ -51,6 +51,7 @@ constexpr int MAX_SECMS = 4;     // SECOND_MILLIS token conversions (ConvertSeco
 constexpr int MAX_LIST = 4;      // NGINX upstream lists (UpstreamListDissector)
 constexpr int MAX_BINIP = 2;     // NGINX $binary_remote_addr values (BinaryIPDissector)
 constexpr int MAX_PAIR = 4;      // request cookie headers / raw-token query strings
+constexpr int MAX_VAL = 8;       // re-dissected remapped values (ScreenResolutionDissector / ModUniqueIdDissector)
 
 // Element kinds = the token regexes of the Apache table
 // (hp/dissectors/tokenformat/TokenParser.java:35-59).
@@ -249,6 +250,30 @@ struct BinipStage {
     int32_t fmt;
 };
 
+// A dissector of the reference's httpdlog-parser jar on a type-remapped value
+// (Parser.addTypeRemapping, core/Parser.java:660-677): the value of a captured
+// token (src_tok >= 0) or of a query parameter (src_q / src_qname, as a
+// derived UriStage's).
+//   VK_SCREEN:   ScreenResolutionDissector (hp/dissectors/ScreenResolutionDissector.java:48-65)
+//                on a SCREENRESOLUTION value: split("x"), parts[0] / parts[1]
+//   VK_UNIQUEID: ModUniqueIdDissector (hp/dissectors/ModUniqueIdDissector.java:104-238)
+//                on a MOD_UNIQUE_ID value: 24 base64 letters -> 18 bytes
+// The guard runs in k_derived_lines (lp_device.h derived_line): a parameter
+// that occurs twice, or a SCREENRESOLUTION value whose split lacks a wanted
+// part (the reference throws ArrayIndexOutOfBoundsException), is FALLBACK.
+// The values are delivered by the device table (table_value.h TC_SCREEN /
+// TC_UNIQUEID) and the host replay (Plan::run_phase) from the located value.
+enum : int32_t { VK_SCREEN = 0, VK_UNIQUEID = 1 };
+enum : int32_t { VW_WIDTH = 1, VW_HEIGHT = 2 };  // ValStage::want of a VK_SCREEN stage
+struct ValStage {
+    int32_t kind;       // VK_*
+    int32_t fmt;
+    int32_t src_tok;    // >= 0: token slot
+    int32_t src_q;      // >= 0: query stage whose parameter src_qname (an index into its names) is the source
+    int32_t src_qname;
+    int32_t want;       // VK_SCREEN: VW_* bits of the requested outputs
+};
+
 // Stages (time / first line / URI) belong to one LogFormat: a line runs the
 // stages of the format it was routed to.  Token slot k of a line is the k-th
 // captured token of that line's format.
@@ -289,6 +314,9 @@ struct Program {
     UriStage uri[MAX_URI];
     QueryStage query[MAX_QUERY];
     alignas(4) uint8_t lit[MAX_LIT];
+    // (appended: the members above keep their offsets)
+    int32_t n_val;
+    ValStage val[MAX_VAL];
     // phase 2 runs (the URI kernel): URI stages or upstream list stages, whose
     // results live in the line's arena region
     __host__ __device__ LP_INLINE bool has_phase2() const { return n_uri > 0 || n_list > 0 || n_pair > 0; }

@@ -37,6 +37,9 @@ enum : int32_t {
     TC_OFFSET,     // LONG: line_off[i]
     TC_LINENO,     // LONG: TableArgs::first_line + i
     TC_STATUS,     // LONG: status[i]
+    // a re-dissected remapped value (lp_program.h ValStage; after the pseudo-columns: their numbers stay)
+    TC_SCREEN,     // a = value stage, b = 0 width / 1 height: that part of split("x") (a sub-span of the value)
+    TC_UNIQUEID,   // a = value stage, b = UQ_* field of the decoded mod_unique_id
 };
 constexpr bool tc_pseudo(int32_t kind) { return kind >= TC_LINE && kind <= TC_STATUS; }
 // ResponseSetCookieDissector outputs (dissectors/ResponseSetCookieDissector.java:49-58)
@@ -44,6 +47,8 @@ enum : int32_t { SC_VALUE, SC_EXPIRES_S /* STRING:expires, seconds */, SC_EXPIRE
                  SC_DOMAIN, SC_COMMENT, SC_PATH };
 enum : int32_t { TF_EPOCH, TF_DAY, TF_MONTHNAME, TF_MONTH, TF_WEEK, TF_WEEKYEAR, TF_YEAR, TF_HOUR, TF_MINUTE,
                  TF_SECOND, TF_MILLI, TF_MICRO, TF_NANO, TF_DATE, TF_TIME };
+// ModUniqueIdDissector outputs, in delivery order (dissectors/ModUniqueIdDissector.java:117-131)
+enum : int32_t { UQ_EPOCH, UQ_IP, UQ_PROCESSID, UQ_COUNTER, UQ_THREADINDEX };
 enum : int32_t { UP_QUERY, UP_PATH, UP_REF, UP_PROTOCOL, UP_HOST, UP_PORT };
 
 struct TableSrc {

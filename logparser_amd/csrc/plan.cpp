@@ -884,6 +884,7 @@ std::unique_ptr<Dissector> mkdis(int cls, const std::string& in) {
     case D_UNIQUEID:
         d->outs = {"TIME.EPOCH:epoch", "IP:ip", "PROCESSID:processid", "COUNTER:counter", "THREAD_INDEX:threadindex"};
         break;
+    case D_SCREENRES: d->outs = {"SCREENWIDTH:width", "SCREENHEIGHT:height"}; break;  // ScreenResolutionDissector.java:73-78
     case D_LOCALIZED: d->outs = {"TIME.LOCALIZEDSTRING:"}; break;
     default: break;
     }
@@ -927,6 +928,19 @@ std::string cleanup_field(const std::string& f) {  // Parser.cleanupFieldValue
 }  // namespace
 
 // ============================================================== planning
+int Plan::add_dissectors(const std::vector<AddDissector>& dissectors, std::string& err) {
+    for (const auto& d : dissectors) {
+        if (d.name != "ScreenResolutionDissector" && d.name != "nl.basjes.parse.httpdlog.dissectors.ScreenResolutionDissector") {
+            err = "unknown dissector class: " + d.name;
+            return LP_E_INVALID;
+        }
+        // registering it twice is the same as once (the first settings are kept)
+        if (!screenres_) screenres_settings_ = d.settings;
+        screenres_ = true;
+    }
+    return LP_OK;
+}
+
 int Plan::build_dissectors(const std::string& logformats, std::string& err) {
     auto root = std::make_unique<Dissector>();
     root->cls = D_ROOT;
@@ -1009,6 +1023,7 @@ int Plan::build_dissectors(const std::string& logformats, std::string& err) {
     dis_.push_back(mkdis(D_SETCOOKIES, "HTTP.SETCOOKIES"));
     dis_.push_back(mkdis(D_SETCOOKIE, "HTTP.SETCOOKIE"));
     dis_.push_back(mkdis(D_UNIQUEID, "MOD_UNIQUE_ID"));
+    if (screenres_) dis_.push_back(mkdis(D_SCREENRES, "SCREENRESOLUTION"));  // Parser.addDissector
     auto c2n = mkdis(D_CLF2NUM, "BYTESCLF");
     c2n->out_type = "BYTES";
     c2n->outs = {"BYTES:"};
@@ -1097,6 +1112,8 @@ int Plan::casts_of(const Dissector& d, const std::string& otype, const std::stri
     case D_UNIQUEID:  // ModUniqueIdDissector.java:76-100
         for (const char* x : {"epoch", "ip", "processid", "counter", "threadindex"}) if (n == x) return SL;
         return NONE;
+    case D_SCREENRES:  // ScreenResolutionDissector.java:81-92
+        return n == "width" || n == "height" ? SL : NONE;
     case D_CLF2NUM: case D_NUM2CLF: case D_SECMILLIS: case D_MS2US:  // TypeConvertBaseDissector.java:36-45
         return n.empty() ? SL : NONE;
     case D_BINIP: return n.empty() ? SL : NONE;  // NginxHttpdLogFormatDissector.java:151-160
@@ -1337,9 +1354,11 @@ void Plan::find_useful(const std::set<std::string>& possible, const std::string&
 }
 
 int Plan::build(const std::string& logformats, const std::vector<std::string>& fields, std::string& err,
-                const std::vector<Remap>& remaps) {
+                const std::vector<Remap>& remaps, const std::vector<AddDissector>& dissectors) {
     gen_ = g_plan_gen.fetch_add(1);
-    int r = build_dissectors(logformats, err);
+    int r = add_dissectors(dissectors, err);
+    if (r != LP_OK) return r;
+    r = build_dissectors(logformats, err);
     if (r != LP_OK) return r;
     // Parser.addTypeRemapping (core/Parser.java:664-677): input trimmed and
     // lower-cased, type trimmed and upper-cased; the first casts given for a
@@ -1403,8 +1422,11 @@ int Plan::build(const std::string& logformats, const std::vector<std::string>& f
 }
 
 int Plan::possible_paths(const std::string& logformats, int max_depth, std::vector<std::string>& out,
-                         std::string& err, const std::vector<Remap>& remaps) {
+                         std::string& err, const std::vector<Remap>& remaps,
+                         const std::vector<AddDissector>& dissectors) {
     Plan p;
+    const int r = p.add_dissectors(dissectors, err);
+    if (r != LP_OK) return r;
     p.build_dissectors(logformats, err);
     std::set<std::string> seen;
     std::function<void(const std::string&, const std::string&, int)> rec = [&](const std::string& base,
@@ -1898,6 +1920,47 @@ void Plan::compile_program() {
                             treg(in.d->out_type + ":" + item, TableSrc{TC_LIST, j, k, vr});
                             walk(O_LITEM, item_code(j, k, vr), in.d->out_type, item, false);
                         }
+                    break;
+                }
+                case D_SCREENRES: case D_UNIQUEID: {
+                    // a dissector on a type-remapped value (lp_program.h ValStage): the
+                    // value of a token or of a query parameter (a derived URI's too);
+                    // k_derived_lines guards it, the device table and the replay
+                    // dissect the located value
+                    if (ok != O_TOKEN && ok != O_QPARAM) {
+                        device_ok_ = false;
+                        why_ = in.d->in_type + " of a value that is neither a token nor a query parameter: " + complete;
+                        return;
+                    }
+                    const int vk = in.cls == D_SCREENRES ? VK_SCREEN : VK_UNIQUEID;
+                    const int key = vk | ((ok == O_QPARAM ? 1 : 0) << 4) | ((ok == O_TOKEN ? tk(oi) : oi) << 8);
+                    if (!val_of_.count(key)) {
+                        if (P.n_val == MAX_VAL) {
+                            device_ok_ = false;
+                            why_ = "too many re-dissected remapped values (at most " + std::to_string(MAX_VAL) + "): " + complete;
+                            return;
+                        }
+                        P.val[P.n_val] = ValStage{vk, cur_fmt, ok == O_TOKEN ? oi : -1, ok == O_QPARAM ? oi / MAX_QNAMES : -1,
+                                                  ok == O_QPARAM ? oi % MAX_QNAMES : 0, 0};
+                        val_of_[key] = P.n_val++;
+                    }
+                    const int vs = val_of_[key];
+                    if (vk == VK_SCREEN) {
+                        if (in.requested.count("width")) {
+                            P.val[vs].want |= VW_WIDTH;
+                            treg("SCREENWIDTH:" + complete + ".width", TableSrc{TC_SCREEN, vs, 0, 0});
+                        }
+                        if (in.requested.count("height")) {
+                            P.val[vs].want |= VW_HEIGHT;
+                            treg("SCREENHEIGHT:" + complete + ".height", TableSrc{TC_SCREEN, vs, 1, 0});
+                        }
+                    } else {
+                        static const char* const uq[][2] = {{"TIME.EPOCH", "epoch"}, {"IP", "ip"}, {"PROCESSID", "processid"},
+                                                            {"COUNTER", "counter"}, {"THREAD_INDEX", "threadindex"}};
+                        for (int k = 0; k < 5; ++k)
+                            if (in.requested.count(uq[k][1]))
+                                treg(std::string(uq[k][0]) + ":" + complete + "." + uq[k][1], TableSrc{TC_UNIQUEID, vs, k, 0});
+                    }
                     break;
                 }
                 default:
@@ -2414,6 +2477,45 @@ void Plan::run_phase(Ctx& c, const Instance& in, const std::string& name, const 
         set_origin(O_CONV, oi);
         c.pool.emplace_back(ip, (size_t)n);
         emit(c, name, in.d->out_type, "", mstr((const uint8_t*)c.pool.back().data(), (uint32_t)n));
+        return;
+    }
+    case D_SCREENRES: {
+        // ScreenResolutionDissector.dissect (dissectors/ScreenResolutionDissector.java:48-65):
+        // split("x") (lp_value.h screen_split), width = parts[0], then height =
+        // parts[1]; k_derived_lines proved the requested parts exist
+        if (v.null || v.is_long || v.len == 0) return;
+        uint32_t wl, ho, hl;
+        const int parts = screen_split(v.p, v.len, wl, ho, hl);
+        if (parts < 0) return;
+        set_origin(O_NONE, 0);
+        if (has("width") && parts >= 1) emit(c, name, "SCREENWIDTH", "width", mstr(v.p, wl));
+        set_origin(O_NONE, 0);
+        if (has("height") && parts >= 2) emit(c, name, "SCREENHEIGHT", "height", mstr(v.p + ho, hl));
+        return;
+    }
+    case D_UNIQUEID: {
+        // ModUniqueIdDissector.dissect (dissectors/ModUniqueIdDissector.java:104-132):
+        // the 18 decoded bytes (lp_value.h unique_id_decode); epoch, ip,
+        // processid, counter, threadindex in that order, the requested only
+        if (v.null || v.is_long || v.len == 0) return;
+        uint32_t f[5];
+        if (!unique_id_decode(v.p, v.len, f)) return;
+        static const char* const ty[] = {"TIME.EPOCH", "IP", "PROCESSID", "COUNTER", "THREAD_INDEX"};
+        static const char* const nm[] = {"epoch", "ip", "processid", "counter", "threadindex"};
+        for (int k = 0; k < 5; ++k) {
+            if (!has(nm[k])) continue;
+            set_origin(O_NONE, 0);
+            if (k == UQ_IP) {
+                char ip[16];
+                const uint32_t n = unique_id_ip(f[1], ip);
+                c.pool.emplace_back(ip, (size_t)n);
+                emit(c, name, ty[k], nm[k], mstr((const uint8_t*)c.pool.back().data(), n));
+            } else {
+                const int64_t l = k == UQ_EPOCH ? (int64_t)f[0] * 1000 : k == UQ_PROCESSID ? (int64_t)f[2]
+                                  : k == UQ_COUNTER ? (int64_t)f[3] : (int64_t)f[4];
+                emit(c, name, ty[k], nm[k], mlong(l));
+            }
+        }
         return;
     }
     case D_NUM2CLF: {

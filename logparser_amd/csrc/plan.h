@@ -44,7 +44,8 @@ struct Format {
 enum DisClass {
     D_ROOT, D_TIMESTAMP, D_TIMESTAMP_ISO, D_FIRSTLINE, D_PROTOCOL, D_URI, D_QUERY, D_COOKIES, D_SETCOOKIES,
     D_SETCOOKIE, D_UNIQUEID, D_CLF2NUM, D_NUM2CLF, D_STRFTIME, D_LOCALIZED,
-    D_BINIP, D_SECMILLIS, D_MS2US, D_UPSTREAM  // NGINX additional dissectors
+    D_BINIP, D_SECMILLIS, D_MS2US, D_UPSTREAM,  // NGINX additional dissectors
+    D_SCREENRES  // ScreenResolutionDissector: only when registered (Parser.addDissector)
 };
 
 struct Dissector {
@@ -131,13 +132,23 @@ struct Remap {
     int casts = CAST_S;
 };
 
+// Parser.addDissector(dissector) (core/Parser.java:154-160) of a dissector of
+// the reference's httpdlog-parser jar that is not registered by default, by
+// class name (simple or fully qualified) with the settings string Hive's
+// "load:" / Pig's "-load:" hands initializeFromSettingsParameter.  Known:
+// ScreenResolutionDissector.
+struct AddDissector {
+    std::string name, settings;
+};
+
 class Plan {
 public:
     // returns LP_OK / LP_E_UNSUPPORTED / error; err filled on error
     int build(const std::string& logformats, const std::vector<std::string>& fields, std::string& err,
-              const std::vector<Remap>& remaps = {});
+              const std::vector<Remap>& remaps = {}, const std::vector<AddDissector>& dissectors = {});
     static int possible_paths(const std::string& logformats, int max_depth, std::vector<std::string>& out,
-                              std::string& err, const std::vector<Remap>& remaps = {});
+                              std::string& err, const std::vector<Remap>& remaps = {},
+                              const std::vector<AddDissector>& dissectors = {});
 
     const Program& program() const { return prog_; }
     // Parser.getCasts(name) (core/Parser.java:127-129): CAST_* bits of a
@@ -187,6 +198,8 @@ public:
     int map_row(const ResultView& R, int64_t i, MapFn fn, void* ctx) const;
 
 private:
+    // LP_OK, or LP_E_INVALID for a class that is not one of the jar's registrable dissectors
+    int add_dissectors(const std::vector<AddDissector>& dissectors, std::string& err);
     int build_dissectors(const std::string& logformats, std::string& err);
     void find_useful(const std::set<std::string>& possible, const std::string& type, const std::string& name,
                      bool is_root);
@@ -207,6 +220,8 @@ private:
     std::string root_type_ = "HTTPLOGLINE";
     std::set<std::string> needed_, useful_, located_;
     std::map<std::string, std::set<std::string>> remaps_;  // Parser.typeRemappings: input path -> new types
+    bool screenres_ = false;            // ScreenResolutionDissector is registered
+    std::string screenres_settings_;    // ... its settings: kept, never used (the separator is always "x", lp_value.h screen_split)
     std::map<std::string, int> casts_;  // castsOfTargets
     uint64_t gen_ = 0;                  // this build's id (the replay's per-thread memo)
     std::map<std::string, std::vector<Instance>> compiled_;
@@ -223,6 +238,7 @@ private:
     std::map<int, int> uri_of_fl_;
     std::map<int, int> query_of_uri_;
     std::map<int, int> uri_of_qp_;         // query stage * MAX_QNAMES + name index -> derived URI stage
+    std::map<int, int> val_of_;            // VK_* | source (token 0 / parameter 1) << 4 | its key << 8 -> value stage
     std::map<std::string, int> qname_of_;  // "query stage:name" -> name index (remapped parameters)
     // device table sources per LogFormat (compile_program): exact paths, the
     // query stages by the name of their query string, and what only the

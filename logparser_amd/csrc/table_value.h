@@ -95,6 +95,36 @@ __device__ __noinline__ void setcookie_attr(const LP_G uint8_t* cp, uint32_t cn,
     }
 }
 
+// A re-dissected remapped value (lp_program.h ValStage; TC_SCREEN / TC_UNIQUEID)
+// on the located value [sp, sp + sn): ScreenResolutionDissector's width / height
+// as a sub-span of the value (the line, or the decoded value in the region),
+// ModUniqueIdDissector's fields as longs, its address formatted into buf
+// (lp_value.h screen_split / unique_id_decode).  Out of line, as
+// setcookie_attr: the other columns keep their registers.  kind / p / n / l
+// as TVal.
+__device__ __noinline__ void remap_value(int tc, int fld, const LP_G uint8_t* sp, uint32_t sn, int& kind,
+                                         const LP_G uint8_t*& p, uint32_t& n, int64_t& l, char* buf) {
+    if (tc == TC_SCREEN) {
+        uint32_t wl, ho, hl;
+        const int parts = screen_split(sp, sn, wl, ho, hl);
+        if (parts <= fld) return;  // no 'x', or (not on an OK line: the guard of derived_line) a missing part
+        kind = 1;
+        p = fld ? sp + ho : sp;
+        n = fld ? hl : wl;
+        return;
+    }
+    uint32_t f[5];
+    if (!unique_id_decode(sp, sn, f)) return;
+    if (fld == UQ_IP) {
+        kind = 3;
+        n = unique_id_ip(f[1], buf);
+        return;
+    }
+    kind = 2;
+    l = fld == UQ_EPOCH ? (int64_t)f[0] * 1000 : fld == UQ_PROCESSID ? (int64_t)f[2] : fld == UQ_COUNTER ? (int64_t)f[3]
+                                                                                                          : (int64_t)f[4];
+}
+
 __device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, const TableSrc& s, int64_t i,
                        const LP_G uint8_t* line, const LP_G uint8_t* region) {
     TVal v;
@@ -282,6 +312,24 @@ __device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, c
             for (int q = 0; q < s.c && same; ++q) same = np[q] == T.names[s.b + q];
             if (same) ref(t[2 * k + 1]);
         }
+        return v;
+    }
+    case TC_SCREEN: case TC_UNIQUEID: {  // the stage's source: a token, or the parameter's one occurrence
+        const ValStage& S = P.val[s.a];
+        const LP_G uint8_t* sp;
+        uint32_t sn;
+        if (S.src_tok >= 0) {
+            if ((C.tok_flags[i] >> S.src_tok) & 1u) return v;  // "-": null, nothing is dissected
+            const uint32_t w = C.tok_span[S.src_tok][i];
+            sp = line + (w & 0xFFFFu);
+            sn = (w >> 16) - (w & 0xFFFFu);
+        } else {
+            uint64_t vref = 0;
+            if (qparam_source(P, S.src_q, S.src_qname, C, i, line, region, vref) != 1) return v;
+            sp = (ref_arena(vref) ? region : line) + ref_off(vref);
+            sn = ref_len(vref);
+        }
+        if (sn) remap_value(s.kind, s.b, sp, sn, v.kind, v.p, v.n, v.l, v.buf);
         return v;
     }
     default:  // TC_NONE, TC_NULL

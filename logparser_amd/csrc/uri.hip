@@ -918,7 +918,8 @@ __global__ __launch_bounds__(PW) void k_uri_overflow(const uint8_t* __restrict__
 // derived_line), after both URI kernels: one line per lane, the sources read
 // in place (the input, or the decoded value in the line's region), every
 // table and rewritten part spilled from the region's shard.  Only launched
-// for programs that have such stages.  Re-counts the wave's statuses.
+// for programs that have such stages or value stages with a guard (also
+// without any URI kernel before it).  Re-counts the wave's statuses.
 __global__ __launch_bounds__(PW) void k_derived_lines(const uint8_t* __restrict__ buf, uint64_t nbytes,
                                                       const DeviceArgs* __restrict__ args) {
     const Program& P = args->prog;
@@ -927,20 +928,39 @@ __global__ __launch_bounds__(PW) void k_derived_lines(const uint8_t* __restrict_
     const int64_t wave = blockIdx.x;
     if (wave * PW >= n_lines || C.meta->cap_ovf) return;
     const WaveLines W = wave_lines(C, wave, n_lines, nbytes);
+    // a program without URI, list or pair stages has no regions (arena_base is not written) and no
+    // per-wave counts: only the value stages' guard of its tokens runs here (lp_program.h ValStage)
+    const bool p2 = P.has_phase2();
     int st = W.active ? (int)C.status[W.li] : -1;
+    const bool was_ok = st == ST_OK;
     if (st == ST_OK) {
         const int fmt = P.n_fmt > 1 ? (int)C.fmt_id[W.li] : 0;
         const LP_G uint8_t* ls = (const LP_G uint8_t*)(buf) + W.s;
         const uint32_t mis = (uint32_t)((uintptr_t)ls & 3);
-        const unsigned long long ab = C.arena_base[W.li];
-        const int shard = (int)(ab / C.shard_cap);
-        Arena R{C.arena + ab, 0, 0};
-        R.top = &C.meta->shard_top[16 * shard];
-        R.base = ab - (unsigned long long)shard * C.shard_cap;
-        R.limit = C.shard_cap;
+        Arena R{C.arena, 0, 0};
+        if (p2) {
+            const unsigned long long ab = C.arena_base[W.li];
+            const int shard = (int)(ab / C.shard_cap);
+            R.p = C.arena + ab;
+            R.top = &C.meta->shard_top[16 * shard];
+            R.base = ab - (unsigned long long)shard * C.shard_cap;
+            R.limit = C.shard_cap;
+        }
         st = derived_line(P, fmt, ls - mis, mis, crlf_len_hbm(buf, W), R, C, W.li);
         if (R.ovf) atomicAdd(&C.meta->arena_ovf, 1ull);  // the batch is re-run with a larger arena
         if (st != ST_OK) C.status[W.li] = (uint8_t)st;
+    }
+    if (!p2) {
+        // the batch's counters come from the chunks' counts (launch_parse): move the lines the guard
+        // took from OK to their new status (the sums commute with the reduction that follows)
+        const unsigned long long bad = __popcll(__ballot(was_ok && st == ST_BAD)),
+                                 fb = __popcll(__ballot(was_ok && st == ST_FALLBACK));
+        if (lane_id() == 0 && (bad | fb)) {
+            atomicAdd(&C.meta->counters[1], 0ull - (bad + fb));
+            if (bad) atomicAdd(&C.meta->counters[2], bad);
+            if (fb) atomicAdd(&C.meta->counters[3], fb);
+        }
+        return;
     }
     const uint32_t ok = (uint32_t)__popcll(__ballot(st == ST_OK)), bad = (uint32_t)__popcll(__ballot(st == ST_BAD));
     if (lane_id() == 0) {
@@ -956,11 +976,13 @@ __global__ __launch_bounds__(PW) void k_derived_lines(const uint8_t* __restrict_
 
 int launch_uri(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s) {
     const int64_t waves = parse_waves(a.cap_lines);
-    if (waves == 0 || !a.uri) return 0;
+    if (waves == 0 || (!a.uri && !a.derived)) return 0;
     const int64_t grid = waves < 1024 ? waves : 1024;
     // most programs have at most two URI and two query stages (the request
     // URI and the referer): an instance keeping two of each
-    if (a.n_uri <= 2 && a.n_query <= 2) {
+    if (!a.uri) {
+        // (only a token's value-stage guard: k_derived_lines alone)
+    } else if (a.n_uri <= 2 && a.n_query <= 2) {
         hipLaunchKernelGGL((k_uri_lines<2, 2>), dim3((unsigned)waves), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
         hipLaunchKernelGGL((k_uri_overflow<2, 2>), dim3((unsigned)grid), dim3(PW), 0, s, a.buf, a.nbytes, d_args);
     } else {
