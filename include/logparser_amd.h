@@ -106,7 +106,43 @@ lp_handle *lp_compile_remapped(const char *logformats, const char *const *paths,
  * SCREENHEIGHT:<path>.height.  The settings are accepted and kept, but the
  * value is split on "x" whatever they say: the reference dissects with a
  * fresh instance that never sees them.  Registering a class twice is the same
- * as once; any other name is LP_E_INVALID.  settings may be NULL (""). */
+ * as once; any other name is LP_E_INVALID.  settings may be NULL ("").
+ *
+ * The GeoIP classes "GeoIPCountryDissector", "GeoIPCityDissector",
+ * "GeoIPASNDissector" and "GeoIPISPDissector" (also
+ * "nl.basjes.parse.httpdlog.dissectors.geoip.<Class>"): settings is the path
+ * of a MaxMind DB file, read when the handle is compiled.  Below every
+ * IP-typed path (%h, %a, %A, $remote_addr, ..., or a token remapped to IP)
+ * they deliver STRING:<p>.continent.name / .continent.code / .country.name /
+ * .country.iso, NUMBER:<p>.country.getconfidence,
+ * BOOLEAN:<p>.country.isineuropeanunion (Country); those and
+ * STRING:<p>.subdivision.name / .subdivision.iso / .city.name / .postal.code /
+ * .location.timezone, NUMBER:<p>.city.confidence / .city.geonameid /
+ * .postal.confidence / .location.accuracyradius / .location.averageincome /
+ * .location.metrocode / .location.populationdensity, and
+ * STRING:<p>.location.latitude / .location.longitude (STRING | DOUBLE: the
+ * value as Double.toString prints it) (City); ASN:<p>.asn.number and
+ * STRING:<p>.asn.organization (ASN); those and STRING:<p>.isp.name /
+ * .isp.organization (ISP).
+ *   LP_E_INVALID      the file cannot be opened or is no valid database (err
+ *                     names the class and the file), also for "" -- from
+ *                     lp_compile_dissectors and lp_possible_paths_dissectors
+ *   LP_E_UNSUPPORTED  (a handle whose every line is FALLBACK, the reason in
+ *                     err) a class registered twice with different paths
+ *                     (the same path twice counts as once); a database whose
+ *                     database_type lacks the class's word (Country, City,
+ *                     ASN, ISP); a requested path that two registered classes
+ *                     deliver from one input (City and Country, ISP and ASN);
+ *                     a source that is no captured token (a query parameter,
+ *                     a cookie, a list item, $binary_remote_addr's value, a
+ *                     mod_unique_id's .ip); more than 8 value stages
+ * A line is LP_LINE_FALLBACK when a looked-up value is anything but a dotted
+ * quad (four decimal parts 0-255, no leading zero) or RFC 4291 text (also
+ * with a dotted quad as its last two groups) of at most 45 bytes -- a host
+ * name would be resolved over DNS by the reference -- or an IPv6 address
+ * against an ip_version 4 database.  "-", an empty value and an address that
+ * is not in the database deliver nothing; an IPv4-mapped address
+ * (::ffff:a.b.c.d) is looked up as IPv4. */
 typedef struct lp_dissector {
     const char *name;
     const char *settings;
@@ -131,7 +167,9 @@ int64_t lp_possible_paths(const char *logformats, int max_depth, char *out, size
 int64_t lp_possible_paths_remapped(const char *logformats, int max_depth, const lp_remap *remaps, int n_remaps,
                                    char *out, size_t cap);
 /* The same with registered dissectors: a path remapped to SCREENRESOLUTION
- * lists its .width / .height below it.  LP_E_INVALID for an unknown class. */
+ * lists its .width / .height below it, every IP-typed path the outputs of the
+ * registered GeoIP classes.  LP_E_INVALID for an unknown class or a GeoIP
+ * database that cannot be read. */
 int64_t lp_possible_paths_dissectors(const char *logformats, int max_depth, const lp_remap *remaps, int n_remaps,
                                      const lp_dissector *dissectors, int n_dissectors, char *out, size_t cap);
 
@@ -252,8 +290,10 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * and k_table_chars over the representatives); then [16] the last complete
  * lp_result_arrow on a device view: its packaging kernels (k_arrow_validity's
  * bitmaps and counts, k_arrow_narrow32), summed over the columns.  [16] is
- * written only for n >= 17: a caller that passes 16 sees what it always saw.
- * Returns the number of values written (at most 17). */
+ * written only for n >= 17: a caller that passes 16 sees what it always saw;
+ * [17], for n >= 18, is k_geoip_lines of the last batch (0 for a program
+ * without a GeoIP stage; it is part of [4]).
+ * Returns the number of values written (at most 18). */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -305,7 +345,9 @@ int lp_last_bytes(lp_handle *h, uint64_t *out, int n);
  *   u_frag (u64 refs) and u_port (i32) per URI stage; q_count (u32) and
  *   q_params (u64 ref of a table of q_count (name ref, value ref) pairs) per
  *   query stage; arena_base (u64, the line's arena region); fmt_id (u8, the
- *   routed LogFormat) with several LogFormats.
+ *   routed LogFormat) with several LogFormats; geo[k] (u32) per GeoIP value
+ *   stage k: the id + 1 of the database record the line's address led to, 0
+ *   when nothing is delivered (the ids are the engine's own, dense per database).
  * A ref is off | len << 32 (len 30 bits); bit 63 set: the bytes are in the
  * line's arena region, else line-relative; bit 62: '&' followed by those
  * bytes.  A q_params table slot whose parameter name was not requested holds
@@ -397,7 +439,9 @@ int lp_casts(lp_handle *h, const char *target);
  * outputs of the dissectors on a remapped token or query parameter
  * (SCREENWIDTH:<p>.width / SCREENHEIGHT:<p>.height of a SCREENRESOLUTION;
  * TIME.EPOCH:<p>.epoch, IP:<p>.ip, PROCESSID:<p>.processid, COUNTER:<p>.counter,
- * THREAD_INDEX:<p>.threadindex of a MOD_UNIQUE_ID) are device columns.
+ * THREAD_INDEX:<p>.threadindex of a MOD_UNIQUE_ID) and the GeoIP classes'
+ * outputs (STRING and LONG columns; location.latitude / .longitude also as
+ * DOUBLE columns) are device columns.
  * LP_E_UNSUPPORTED names a path whose value only the host replay
  * derives (a converter applied to an already converted value) or a DOUBLE
  * column of a string-valued path (Double.parseDouble): build those from a

@@ -373,7 +373,7 @@ def get_possible_paths(logformat, max_depth=15, remaps=(), dissectors=()):
     n = lib().lp_possible_paths_dissectors(logformat.encode(), max_depth, arr, n_rm, dz, n_dz, out, cap)
     if n == LP_E_INVALID:  # (cap > 0 and an empty list is length 0, never -1: the arguments were refused)
         names = [bytes(dz[k].name).decode() for k in range(n_dz)]
-        raise InvalidDissectorException("unknown dissector class among %r" % names if names
+        raise InvalidDissectorException("unknown dissector class, or a GeoIP database that cannot be read, among %r" % names if names
                                         else "lp_possible_paths_dissectors: invalid arguments")
     if n < 0:
         raise InvalidDissectorException("possible paths overflow")
@@ -852,6 +852,10 @@ class BatchResult:
         {"values": k_table_values, "scans": offset scans, "chars": k_table_chars}"""
         return dict(zip(("values", "scans", "chars"), self._timing(5, 8)))
 
+    def geoip_timing(self):
+        """HIP-event ms of k_geoip_lines in the last batch (lp_last_timing [17]; 0 without a GeoIP stage)"""
+        return self._timing(17, 18)[0]
+
     def _dict_call(self, res, paths, first, count, rows_p, threads, bufs, alloc, ptr):
         """lp_result_table_dict / _rows into bufs (per path [valid, index,
         dict_off, dict_chars]); after LP_E_NOMEM the dictionary's arrays are
@@ -1140,11 +1144,21 @@ class HttpdLoglineParser:
     # Parser.addDissector (core/Parser.java:154-160) of a dissector of the
     # reference's httpdlog-parser jar that is not there by default
     def add_dissector(self, name, settings=""):
-        """Register a dissector by class name (ScreenResolutionDissector, or
-        its fully qualified name as Hive's "load:" / Pig's "-load:" give it)
-        with its settings string.  The settings are kept but, as in the
+        """Register a dissector by class name (simple, or fully qualified as
+        Hive's "load:" / Pig's "-load:" give it) with its settings string.
+
+        ScreenResolutionDissector: the settings are kept but, as in the
         reference, never reach the instance that dissects: a SCREENRESOLUTION
-        is always split on "x"."""
+        is always split on "x".
+
+        GeoIPCountryDissector / GeoIPCityDissector / GeoIPASNDissector /
+        GeoIPISPDissector: the settings are the path of the MaxMind DB file,
+        e.g. add_dissector("GeoIPCityDissector", "/path/to.mmdb").  Their
+        outputs appear below every IP-typed path (country.name, city.name,
+        location.latitude, asn.number, ...: get_possible_paths); a file that
+        cannot be read as a database raises InvalidDissectorException when the
+        parser is compiled.  A line whose address is a host name or a legacy
+        form (anything but a dotted quad or RFC 4291 text) is FALLBACK."""
         self._dissectors.append((name, settings or ""))
         self._close()
         return self

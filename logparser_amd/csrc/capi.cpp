@@ -139,6 +139,9 @@ struct lp_handle {
     DevBuf input, chunk, line_off, cols, arena, meta, waves, args, route, ovf, hist;
     DevBuf cstate;  // chunked parse: look-back words, per-chunk counts, queued lines
     DevBuf targs, tscratch;  // device table (lp_result_table on a device view)
+    // the GeoIP stages' images on this handle's device (lp_geoip.h): a tree per database, a
+    // field table and its byte pool per stage; uploaded at compile time, released by lp_free
+    DevBuf geo_tree[lp::N_GEODB], geo_fields[lp::MAX_VAL], geo_pool[lp::MAX_VAL];
     lp::DeviceArgs host_args{};
     lp::Columns C{};
     std::vector<ColSpec> specs;
@@ -161,7 +164,8 @@ struct lp_handle {
     uint64_t arena_ovf = 0;        // arena overflow events of the last batch's final run (its lines FALLBACK)
     int64_t first_line = 0;        // global number of the last batch's first line
     int64_t next_line = 0;         // ... of the next batch's (lp_parse_batch continues the numbering)
-    hipEvent_t ev[5]{};  // batch start, index done, parse start, batch end, parse kernels done
+    hipEvent_t ev[7]{};  // batch start, index done, parse start, batch end, parse kernels done, k_geoip_lines start / end
+    float geo_ms = 0;    // k_geoip_lines of the last batch (lp_last_timing [17])
     hipEvent_t tev[6]{}; // the device table calls' phase events (PhaseTimer): one pool, the calls are serialised
     // lp_last_timing [5..16], each family's last successful device call: the table's values / scans /
     // bytes phases; the map columns' count / entries / fill phases, summed over the columns;
@@ -226,6 +230,8 @@ void build_specs(lp_handle* h) {
     }
     for (int k = 0; k < P.n_secms; ++k) add("sm_ms", k, 8, &C.sm_ms[k]);
     for (int k = 0; k < P.n_binip; ++k) add("bip", k, 4, &C.bip[k]);
+    for (int k = 0; k < P.n_val; ++k)
+        if (P.val[k].kind == lp::VK_GEOIP) add("geo", k, 4, &C.geo[k]);  // (k_geoip_lines': neither kernel family's bytes)
     for (int f = 0; f < P.n_fl; ++f) {
         add("fl_kind", f, 4, &C.fl_kind[f]);
         add("fl_method", f, 4, &C.fl_method[f]);
@@ -327,11 +333,36 @@ void make_view(lp_handle* h, const lp_result& r, lp::ResultView& V) {
         else if (nm == "l_count") V.l_count[i] = (const uint32_t*)p;
         else if (nm == "l_tab") V.l_tab[i] = (const uint64_t*)p;
         else if (nm == "bip") V.bip[i] = (const uint32_t*)p;
+        else if (nm == "geo") V.geo[i] = (const uint32_t*)p;
         else if (nm == "p_count") V.p_count[i] = (const uint32_t*)p;
         else if (nm == "p_tab") V.p_tab[i] = (const uint64_t*)p;
         else if (nm == "fmt_id") V.fmt_id = (const uint8_t*)p;
     }
     if (!V.arena) V.arena_base = nullptr;
+}
+
+// The GeoIP stages' images to the handle's device, their pointers into h->C
+// (copied into every batch's DeviceArgs): one tree per database, a field
+// table and pool per stage.
+bool upload_geo(lp_handle* h) {
+    const lp::Program& P = h->plan.program();
+    auto put = [](DevBuf& b, const void* src, size_t bytes) {
+        if (!b.ensure(bytes + 16)) return false;
+        return bytes == 0 || hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    for (int k = 0; k < P.n_val; ++k) {
+        if (P.val[k].kind != lp::VK_GEOIP) continue;
+        const lp::GeoImage& G = h->plan.geo_image(k);
+        DevBuf& T = h->geo_tree[P.val[k].src_qname];
+        if (!T.p && !put(T, G.tree->data(), 8 * G.tree->size())) return false;
+        if (!put(h->geo_fields[k], G.fields.data(), sizeof(lp::GeoField) * G.fields.size())) return false;
+        if (!put(h->geo_pool[k], G.pool.data(), G.pool.size())) return false;
+        h->C.geo_tree[k] = T.as<uint64_t>();
+        h->C.geo_fields[k] = h->geo_fields[k].as<uint64_t>();
+        h->C.geo_pool[k] = h->geo_pool[k].as<uint8_t>();
+        h->C.geo_records[k] = G.n_records;
+    }
+    return true;
 }
 
 // Enqueue the whole batch (index, routing, parse) with the current
@@ -474,6 +505,9 @@ int enqueue(lp_handle* h, bool sync_count) {
             if (e.nlit && !e.last && ((e.kind == lp::EK_NOSPACE && !e.det) || e.kind == lp::EK_NOSPACE3))
                 pl.lit_aware = true;
         }
+        for (int k = 0; k < P.n_val; ++k) pl.geoip = pl.geoip || P.val[k].kind == lp::VK_GEOIP;
+        pl.geo_event[0] = h->ev[5];
+        pl.geo_event[1] = h->ev[6];
         pl.simple = simple_program(P);
         pl.shape = h->fixed_shape && !pl.lit_aware ? fixed_shape_program(P, h->force_direct) : lp::FS_NONE;
         h->last_launch = pl;
@@ -593,6 +627,9 @@ int finish(lp_handle* h) {
         hipEventElapsedTime(&d, h->ev[2], h->ev[4]);
         hipEventElapsedTime(&e, h->ev[4], h->ev[3]);
         h->ms[0] = a; h->ms[1] = b; h->ms[2] = c; h->ms[3] = d; h->ms[4] = e;
+        h->geo_ms = 0;
+        if (h->plan.device_ok() && h->last_launch.geoip && lp::parse_waves(h->cap_lines) > 0)
+            hipEventElapsedTime(&h->geo_ms, h->ev[5], h->ev[6]);
         return LP_OK;
     }
 }
@@ -728,6 +765,13 @@ lp_handle* lp_compile_dissectors(const char* logformats, const char* const* path
     for (auto& ev : h->tev) hipEventCreate(&ev);
     h->have_events = true;
     if (!h->meta.ensure(sizeof(lp::Meta))) { if (status) *status = LP_E_NOMEM; return nullptr; }
+    if (st == LP_OK && !upload_geo(h.get())) {
+        lp_handle* raw = h.release();
+        lp_free(raw);
+        if (status) *status = LP_E_NOMEM;
+        set_err(err, errlen, "no device memory for the GeoIP images");
+        return nullptr;
+    }
     if (status) *status = st;
     return h.release();
 }
@@ -739,6 +783,9 @@ void lp_free(lp_handle* h) {
     for (auto* b : {&h->input, &h->chunk, &h->line_off, &h->cols, &h->arena, &h->meta, &h->waves, &h->args, &h->route,
                     &h->ovf, &h->hist, &h->cstate, &h->targs, &h->tscratch})
         b->release();
+    for (auto& b : h->geo_tree) b.release();
+    for (auto& b : h->geo_fields) b.release();
+    for (auto& b : h->geo_pool) b.release();
     if (h->have_events) {
         for (auto& ev : h->ev) hipEventDestroy(ev);
         for (auto& ev : h->tev) hipEventDestroy(ev);
@@ -974,7 +1021,9 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     for (int k = 5; k < n && k < 16; ++k) out[k] = h->tms[k - 5];
     if (n < 17) return n < 16 ? n : 16;  // (a caller of the 16 values sees what it always saw)
     out[16] = h->tms[TMS_ARROW];
-    return 17;
+    if (n < 18) return 17;
+    out[17] = h->geo_ms;
+    return 18;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1246,7 +1295,8 @@ static int table_device(lp_handle* h, const lp_result* r, int64_t first, int64_t
                                          (x.kind == lp::TC_URI && x.b == lp::UP_PORT) ||
                                          (x.kind == lp::TC_TIME && x.b != lp::TF_MONTHNAME && x.b != lp::TF_DATE &&
                                           x.b != lp::TF_TIME) ||
-                                         x.kind == lp::TC_SECMS || x.kind == lp::TC_LIST_MS;
+                                         x.kind == lp::TC_SECMS || x.kind == lp::TC_LIST_MS ||
+                                         (x.kind == lp::TC_GEOIP && x.c != lp::GK_STRING);  // (a DOUBLE field: its f64)
                 // a SECOND_MILLIS list item: digits '.' digits, parsed on the device (decimal_to_double)
                 const bool decimal = x.kind == lp::TC_LIST && h->plan.program().list[x.a].secms;
                 if (!long_valued && !decimal) return LP_E_UNSUPPORTED;

@@ -51,6 +51,8 @@ struct ParseLaunch {
     bool multi = false;         // several LogFormats (match words in the chunk kernel, then the routing scan)
     int shape = 0;              // the fixed shape whose chunk kernel instance parses the program (lp_fixed.h
                                 // fixed_shape_of; FS_NONE: the instances per program class)
+    bool geoip = false;         // the program has GeoIP value stages (k_geoip_lines after the URI kernels)
+    void* geo_event[2] = {nullptr, nullptr};  // hipEvent_t recorded before / after k_geoip_lines
 };
 // The chunked parse kernel's geometry: cb input bytes per chunk (one wave
 // each), an LDS window of win_cap bytes (the chunk, 64 bytes before it, the
@@ -76,6 +78,8 @@ int launch_chunks_fixed(const ParseLaunch& a, const DeviceArgs* d_args, const Ch
                         hipStream_t s);
 // the URI kernels of a launch (uri.hip)
 int launch_uri(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s);
+// k_geoip_lines of a launch whose program has GeoIP value stages (geoip.hip)
+int launch_geoip(const ParseLaunch& a, const DeviceArgs* d_args, hipStream_t s);
 // meta->counters[0..5] += the sum of n_entries count records (per_group: of
 // 64-line groups, only those holding the batch's meta->n_lines lines)
 int launch_reduce_counts(const uint32_t* d_wave_counts, int64_t n_entries, bool per_group, Meta* d_meta, hipStream_t s);

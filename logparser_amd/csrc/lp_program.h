@@ -51,7 +51,7 @@ constexpr int MAX_SECMS = 4;     // SECOND_MILLIS token conversions (ConvertSeco
 constexpr int MAX_LIST = 4;      // NGINX upstream lists (UpstreamListDissector)
 constexpr int MAX_BINIP = 2;     // NGINX $binary_remote_addr values (BinaryIPDissector)
 constexpr int MAX_PAIR = 4;      // request cookie headers / raw-token query strings
-constexpr int MAX_VAL = 8;       // re-dissected remapped values (ScreenResolutionDissector / ModUniqueIdDissector)
+constexpr int MAX_VAL = 8;       // re-dissected values (ScreenResolutionDissector / ModUniqueIdDissector / GeoIP lookups)
 
 // Element kinds = the token regexes of the Apache table
 // (hp/dissectors/tokenformat/TokenParser.java:35-59).
@@ -263,15 +263,23 @@ struct BinipStage {
 // part (the reference throws ArrayIndexOutOfBoundsException), is FALLBACK.
 // The values are delivered by the device table (table_value.h TC_SCREEN /
 // TC_UNIQUEID) and the host replay (Plan::run_phase) from the located value.
-enum : int32_t { VK_SCREEN = 0, VK_UNIQUEID = 1 };
+//   VK_GEOIP:    a GeoIP dissector (hp/dissectors/geoip/AbstractGeoIPDissector.java:93-110)
+//                on an IP token (src_tok; src_qname = the class's database, want =
+//                the wanted fields' bits, lp_geoip.h GF_*).  k_geoip_lines
+//                (geoip.hip) parses the address, walks the database's tree and
+//                writes the record id + 1 into column geo[stage] (0: no outputs);
+//                an address text outside the decided subset is FALLBACK.  The
+//                table (TC_GEOIP) and the replay gather the fields from the
+//                stage's field table.
+enum : int32_t { VK_SCREEN = 0, VK_UNIQUEID = 1, VK_GEOIP = 2 };
 enum : int32_t { VW_WIDTH = 1, VW_HEIGHT = 2 };  // ValStage::want of a VK_SCREEN stage
 struct ValStage {
     int32_t kind;       // VK_*
     int32_t fmt;
     int32_t src_tok;    // >= 0: token slot
     int32_t src_q;      // >= 0: query stage whose parameter src_qname (an index into its names) is the source
-    int32_t src_qname;
-    int32_t want;       // VK_SCREEN: VW_* bits of the requested outputs
+    int32_t src_qname;  // (VK_GEOIP: the database, 0 Country / 1 City / 2 ASN / 3 ISP)
+    int32_t want;       // VK_SCREEN: VW_* bits of the requested outputs; VK_GEOIP: bit f = field GF_f
 };
 
 // Stages (time / first line / URI) belong to one LogFormat: a line runs the
@@ -450,6 +458,13 @@ struct Columns {
     LP_G uint32_t* ovf_lines;            // [cap_lines] line numbers
     LP_G uint32_t* deferred_chunks;      // [n_chunks] chunks left to the deferred pass (Meta::deferred of them)
     int64_t cap_lines;                   // lines the columns hold
+    // (appended: the members above keep their offsets) the GeoIP value stages
+    // (lp_geoip.h): stage k's result column, and its images on this device
+    LP_G uint32_t* geo[MAX_VAL];             // [n] the line's record id + 1, 0: no outputs
+    const LP_G uint64_t* geo_tree[MAX_VAL];  // the tree image, as u64 words
+    const LP_G uint64_t* geo_fields[MAX_VAL];// the field table: two u64 per GeoField (v; off | len << 32)
+    const LP_G uint8_t* geo_pool[MAX_VAL];   // ... its bytes
+    uint32_t geo_records[MAX_VAL];           // record ids of the stage's database
 };
 
 }  // namespace lp

@@ -40,6 +40,8 @@ enum : int32_t {
     // a re-dissected remapped value (lp_program.h ValStage; after the pseudo-columns: their numbers stay)
     TC_SCREEN,     // a = value stage, b = 0 width / 1 height: that part of split("x") (a sub-span of the value)
     TC_UNIQUEID,   // a = value stage, b = UQ_* field of the decoded mod_unique_id
+    TC_GEOIP,      // a = value stage, b = GF_* field, c = GK_* kind: the field of the record geo[a][row] names,
+                   // gathered from the stage's field table (lp_geoip.h)
 };
 constexpr bool tc_pseudo(int32_t kind) { return kind >= TC_LINE && kind <= TC_STATUS; }
 // ResponseSetCookieDissector outputs (dissectors/ResponseSetCookieDissector.java:49-58)

@@ -233,6 +233,7 @@ int launch_parse(const ParseLaunch& a, const DeviceArgs* d_args, const Columns& 
     }
     if (a.mid_event) hipEventRecord((hipEvent_t)a.mid_event, s);
     if (launch_uri(a, d_args, s) != 0) return -1;
+    if (launch_geoip(a, d_args, s) != 0) return -1;  // (its status changes reach the counters by atomics)
     // without URI stages the chunks' counts (plus the queued lines' own
     // atomics); with them the URI kernel re-counted every 64-line group
     if (a.uri) return launch_reduce_counts(C.wave_counts, waves, true, C.meta, s);

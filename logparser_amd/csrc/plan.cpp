@@ -15,6 +15,7 @@
 //                                         core/Parser.java:237-490, 904-1012
 //   Parsable.addDissection                core/Parsable.java:142-193 (replay)
 #include "plan.h"
+#include "lp_mmdb.h"
 
 #include <atomic>
 #include <unordered_map>
@@ -861,6 +862,124 @@ const char* TS_OUTS[] = {
     "TIME.HOUR:hour_utc", "TIME.MINUTE:minute_utc", "TIME.SECOND:second_utc", "TIME.MILLISECOND:millisecond_utc",
     "TIME.MICROSECOND:microsecond_utc", "TIME.NANOSECOND:nanosecond_utc", "TIME.DATE:date_utc", "TIME.TIME:time_utc"};
 
+// The GeoIP dissectors' outputs by field id (lp_geoip.h GF_*), in delivery order:
+// getPossibleOutput and the casts of prepareForDissect (hp/dissectors/geoip/
+// GeoIPCountryDissector.java:50-111, GeoIPCityDissector.java:52-188,
+// GeoIPASNDissector.java:47-75, GeoIPISPDissector.java:45-77), and where
+// geoip2 2.12.0's model classes read each from the record's map: a key path
+// (names_en: then names["en"], the DatabaseReader's default locale list;
+// "subdivisions": the array's last element, getMostSpecificSubdivision).
+struct GeoFieldDef {
+    const char* type;
+    const char* name;
+    int kind;             // GK_*
+    const char* path[2];  // keys from the record's map
+    bool names_en;
+    bool skip_null;       // not delivered when null (GeoIPCityDissector.java:260-277)
+};
+const GeoFieldDef GEO_FIELDS[GF_COUNT] = {
+    {"STRING", "continent.name", GK_STRING, {"continent", nullptr}, true, false},
+    {"STRING", "continent.code", GK_STRING, {"continent", "code"}, false, false},
+    {"STRING", "country.name", GK_STRING, {"country", nullptr}, true, false},
+    {"STRING", "country.iso", GK_STRING, {"country", "iso_code"}, false, false},
+    {"NUMBER", "country.getconfidence", GK_LONG, {"country", "confidence"}, false, false},
+    {"BOOLEAN", "country.isineuropeanunion", GK_LONG, {"country", "is_in_european_union"}, false, false},
+    {"STRING", "subdivision.name", GK_STRING, {"subdivisions", nullptr}, true, false},
+    {"STRING", "subdivision.iso", GK_STRING, {"subdivisions", "iso_code"}, false, false},
+    {"STRING", "city.name", GK_STRING, {"city", nullptr}, true, false},
+    {"NUMBER", "city.confidence", GK_LONG, {"city", "confidence"}, false, false},
+    {"NUMBER", "city.geonameid", GK_LONG, {"city", "geoname_id"}, false, false},
+    {"STRING", "postal.code", GK_STRING, {"postal", "code"}, false, false},
+    {"NUMBER", "postal.confidence", GK_LONG, {"postal", "confidence"}, false, false},
+    {"STRING", "location.latitude", GK_DOUBLE, {"location", "latitude"}, false, false},
+    {"STRING", "location.longitude", GK_DOUBLE, {"location", "longitude"}, false, false},
+    {"STRING", "location.timezone", GK_STRING, {"location", "time_zone"}, false, false},
+    {"NUMBER", "location.accuracyradius", GK_LONG, {"location", "accuracy_radius"}, false, false},
+    {"NUMBER", "location.averageincome", GK_LONG, {"location", "average_income"}, false, true},
+    {"NUMBER", "location.metrocode", GK_LONG, {"location", "metro_code"}, false, true},
+    {"NUMBER", "location.populationdensity", GK_LONG, {"location", "population_density"}, false, true},
+    {"ASN", "asn.number", GK_LONG, {"autonomous_system_number", nullptr}, false, false},
+    {"STRING", "asn.organization", GK_STRING, {"autonomous_system_organization", nullptr}, false, false},
+    {"STRING", "isp.name", GK_STRING, {"isp", nullptr}, false, false},
+    {"STRING", "isp.organization", GK_STRING, {"organization", nullptr}, false, false},
+};
+// the fields of a class: City extends Country, ISP extends ASN
+void geo_class_fields(int cls, int& first, int& last) {
+    first = cls == D_GEOIP_ASN || cls == D_GEOIP_ISP ? GF_ASN_NUMBER : GF_CONTINENT_NAME;
+    last = cls == D_GEOIP_COUNTRY ? GF_COUNTRY_EU : cls == D_GEOIP_CITY ? GF_POPULATIONDENSITY
+           : cls == D_GEOIP_ASN ? GF_ASN_ORGANIZATION : GF_ISP_ORGANIZATION;
+}
+const char* const GEO_CLASS[N_GEODB] = {"GeoIPCountryDissector", "GeoIPCityDissector", "GeoIPASNDissector",
+                                        "GeoIPISPDissector"};
+// the word DatabaseReader.country / city / asn / isp looks for in database_type (geoip2 DatabaseReader.get)
+const char* const GEO_DBTYPE[N_GEODB] = {"Country", "City", "ASN", "ISP"};
+
+// Field f of the record whose map is at data offset off: what the model
+// object's getter returns, as a GeoField whose strings go to pool (one copy
+// per distinct string).  A key that is absent, or holds another type than the
+// getter's, is null; is_in_european_union absent is false.
+GeoField geo_field(const mmdb::Db& D, uint32_t off, int f, std::string& pool,
+                   std::map<std::string, uint32_t>& pooled) {
+    using namespace mmdb;
+    const GeoFieldDef& F = GEO_FIELDS[f];
+    GeoField out{0, GEO_NULL, 0};
+    auto text = [&](const char* p, size_t n) {
+        const std::string t(p, n);
+        auto it = pooled.find(t);
+        if (it == pooled.end()) {
+            it = pooled.emplace(t, (uint32_t)pool.size()).first;
+            pool += t;
+        }
+        out.off = it->second;
+        out.len = (uint32_t)n;
+    };
+    size_t pos = off;
+    Val cur;
+    bool found = decode(D.data, pos, cur) && cur.type == T_MAP;
+    for (int k = 0; k < 2 && found && F.path[k]; ++k) {
+        Val nx;
+        if (!map_get(D.data, cur, F.path[k], nx, found)) found = false;
+        if (found && k == 0 && !strcmp(F.path[0], "subdivisions")) {
+            Val last;
+            found = nx.type == T_ARRAY && nx.n > 0 && array_get(D.data, nx, nx.n - 1, last);
+            nx = last;
+        }
+        cur = nx;
+    }
+    if (found && F.names_en) {
+        Val names, en;
+        bool has = false;
+        found = cur.type == T_MAP && map_get(D.data, cur, "names", names, has) && has && names.type == T_MAP;
+        if (found) found = map_get(D.data, names, "en", en, has) && has;
+        cur = en;
+    }
+    if (f == GF_COUNTRY_EU) {  // Country.isInEuropeanUnion(): a primitive boolean, false when absent
+        out.off = 0;
+        out.v = found && cur.type == T_BOOLEAN && cur.u ? 1 : 0;
+        return out;
+    }
+    if (!found) return out;
+    switch (F.kind) {
+    case GK_STRING:
+        if (cur.type == T_UTF8) text((const char*)cur.s, cur.n);
+        break;
+    case GK_LONG:
+        // (geoip2's getters are Integer / Long: a uint64 past 2^61 is none of theirs, and the
+        // table's value words hold a long of 62 bits, lp_table.h SW_LONG)
+        if ((cur.type == T_UINT16 || cur.type == T_UINT32 || cur.type == T_UINT64) && cur.u < (1ull << 61)) { out.off = 0; out.v = cur.u; }
+        else if (cur.type == T_INT32) { out.off = 0; out.v = (uint64_t)cur.i; }
+        break;
+    default:
+        if (cur.type == T_DOUBLE || cur.type == T_FLOAT) {
+            memcpy(&out.v, &cur.d, 8);
+            const std::string t = java_double(cur.d);
+            text(t.data(), t.size());
+        }
+        break;
+    }
+    return out;
+}
+
 std::unique_ptr<Dissector> mkdis(int cls, const std::string& in) {
     auto d = std::make_unique<Dissector>();
     d->cls = cls;
@@ -886,6 +1005,12 @@ std::unique_ptr<Dissector> mkdis(int cls, const std::string& in) {
         break;
     case D_SCREENRES: d->outs = {"SCREENWIDTH:width", "SCREENHEIGHT:height"}; break;  // ScreenResolutionDissector.java:73-78
     case D_LOCALIZED: d->outs = {"TIME.LOCALIZEDSTRING:"}; break;
+    case D_GEOIP_COUNTRY: case D_GEOIP_CITY: case D_GEOIP_ASN: case D_GEOIP_ISP: {
+        int first, last;
+        geo_class_fields(cls, first, last);
+        for (int f = first; f <= last; ++f) d->outs.push_back(std::string(GEO_FIELDS[f].type) + ":" + GEO_FIELDS[f].name);
+        break;
+    }
     default: break;
     }
     return d;
@@ -928,15 +1053,50 @@ std::string cleanup_field(const std::string& f) {  // Parser.cleanupFieldValue
 }  // namespace
 
 // ============================================================== planning
+Plan::Plan() = default;
+Plan::~Plan() = default;
+
 int Plan::add_dissectors(const std::vector<AddDissector>& dissectors, std::string& err) {
     for (const auto& d : dissectors) {
-        if (d.name != "ScreenResolutionDissector" && d.name != "nl.basjes.parse.httpdlog.dissectors.ScreenResolutionDissector") {
+        if (d.name == "ScreenResolutionDissector" || d.name == "nl.basjes.parse.httpdlog.dissectors.ScreenResolutionDissector") {
+            // registering it twice is the same as once (the first settings are kept)
+            if (!screenres_) screenres_settings_ = d.settings;
+            screenres_ = true;
+            continue;
+        }
+        // a GeoIP class: its settings are the database's path (AbstractGeoIPDissector.java:55-59);
+        // prepareForRun opens it, an IOException is an InvalidDissectorException naming the
+        // class and the file (:72-84)
+        static const std::string pkg = "nl.basjes.parse.httpdlog.dissectors.geoip.";
+        const std::string simple = d.name.compare(0, pkg.size(), pkg) == 0 ? d.name.substr(pkg.size()) : d.name;
+        int g = -1;
+        for (int k = 0; k < N_GEODB; ++k)
+            if (simple == GEO_CLASS[k]) g = k;
+        if (g < 0) {
             err = "unknown dissector class: " + d.name;
             return LP_E_INVALID;
         }
-        // registering it twice is the same as once (the first settings are kept)
-        if (!screenres_) screenres_settings_ = d.settings;
-        screenres_ = true;
+        if (geodb_[g]) {
+            if (geodb_path_[g] != d.settings && device_ok_) {
+                device_ok_ = false;
+                why_ = std::string(GEO_CLASS[g]) + " registered twice with different databases: " + geodb_path_[g] +
+                       ", " + d.settings;
+            }
+            continue;
+        }
+        auto db = std::make_unique<mmdb::Db>();
+        std::string why;
+        if (!mmdb::load(*db, d.settings, why)) {
+            err = "InvalidDissectorException: " + pkg + GEO_CLASS[g] + ":" + why;
+            return LP_E_INVALID;
+        }
+        if (db->database_type.find(GEO_DBTYPE[g]) == std::string::npos && device_ok_) {
+            // (the reference throws an unchecked exception on the first line)
+            device_ok_ = false;
+            why_ = std::string(GEO_CLASS[g]) + " on a database of type " + db->database_type + ": " + d.settings;
+        }
+        geodb_[g] = std::move(db);
+        geodb_path_[g] = d.settings;
     }
     return LP_OK;
 }
@@ -1024,6 +1184,8 @@ int Plan::build_dissectors(const std::string& logformats, std::string& err) {
     dis_.push_back(mkdis(D_SETCOOKIE, "HTTP.SETCOOKIE"));
     dis_.push_back(mkdis(D_UNIQUEID, "MOD_UNIQUE_ID"));
     if (screenres_) dis_.push_back(mkdis(D_SCREENRES, "SCREENRESOLUTION"));  // Parser.addDissector
+    for (int g = 0; g < N_GEODB; ++g)
+        if (geodb_[g]) dis_.push_back(mkdis(D_GEOIP_COUNTRY + g, "IP"));  // AbstractGeoIPDissector.INPUT_TYPE
     auto c2n = mkdis(D_CLF2NUM, "BYTESCLF");
     c2n->out_type = "BYTES";
     c2n->outs = {"BYTES:"};
@@ -1114,6 +1276,15 @@ int Plan::casts_of(const Dissector& d, const std::string& otype, const std::stri
         return NONE;
     case D_SCREENRES:  // ScreenResolutionDissector.java:81-92
         return n == "width" || n == "height" ? SL : NONE;
+    case D_GEOIP_COUNTRY: case D_GEOIP_CITY: case D_GEOIP_ASN: case D_GEOIP_ISP: {
+        // STRING_ONLY / STRING_OR_LONG / STRING_OR_DOUBLE (GEO_FIELDS)
+        int first, last;
+        geo_class_fields(d.cls, first, last);
+        for (int f = first; f <= last; ++f)
+            if (n == GEO_FIELDS[f].name)
+                return GEO_FIELDS[f].kind == GK_STRING ? SO : GEO_FIELDS[f].kind == GK_LONG ? SL : (CAST_S | CAST_D);
+        return NONE;
+    }
     case D_CLF2NUM: case D_NUM2CLF: case D_SECMILLIS: case D_MS2US:  // TypeConvertBaseDissector.java:36-45
         return n.empty() ? SL : NONE;
     case D_BINIP: return n.empty() ? SL : NONE;  // NginxHttpdLogFormatDissector.java:151-160
@@ -1960,7 +2131,54 @@ void Plan::compile_program() {
                         for (int k = 0; k < 5; ++k)
                             if (in.requested.count(uq[k][1]))
                                 treg(std::string(uq[k][0]) + ":" + complete + "." + uq[k][1], TableSrc{TC_UNIQUEID, vs, k, 0});
+                        // its address is formatted per row, never a column: nothing to look up from
+                        if (useful_.count(complete + ".ip") && compiled_.count("IP:" + complete + ".ip")) {
+                            device_ok_ = false;
+                            why_ = "a dissector on the address of a mod_unique_id: " + complete + ".ip";
+                            return;
+                        }
                     }
+                    break;
+                }
+                case D_GEOIP_COUNTRY: case D_GEOIP_CITY: case D_GEOIP_ASN: case D_GEOIP_ISP: {
+                    // a GeoIP lookup (lp_program.h ValStage, VK_GEOIP): k_geoip_lines parses the
+                    // token and walks the class's database, the table and the replay gather the
+                    // record's fields
+                    if (ok != O_TOKEN) {
+                        device_ok_ = false;
+                        why_ = "GeoIP lookup of a value that is not a captured token: " + complete;
+                        return;
+                    }
+                    // two registered classes that deliver one path from this input (City and
+                    // Country, ISP and ASN): the reference delivers it twice
+                    for (const auto& other : it->second)
+                        if (&other != &in && dis_geoip(other.cls))
+                            for (const auto& r : in.requested)
+                                if (other.requested.count(r)) {
+                                    device_ok_ = false;
+                                    why_ = "two GeoIP dissectors deliver " + complete + "." + r;
+                                    return;
+                                }
+                    const int g = in.cls - D_GEOIP_COUNTRY;
+                    const int key = VK_GEOIP | (g << 5) | (tk(oi) << 8);
+                    if (!val_of_.count(key)) {
+                        if (P.n_val == MAX_VAL) {
+                            device_ok_ = false;
+                            why_ = "too many re-dissected values (at most " + std::to_string(MAX_VAL) + "): " + complete;
+                            return;
+                        }
+                        P.val[P.n_val] = ValStage{VK_GEOIP, cur_fmt, oi, -1, g, 0};
+                        val_of_[key] = P.n_val++;
+                    }
+                    const int vs = val_of_[key];
+                    int first, last;
+                    geo_class_fields(in.cls, first, last);
+                    for (int f = first; f <= last; ++f)
+                        if (in.requested.count(GEO_FIELDS[f].name)) {
+                            P.val[vs].want |= 1 << f;
+                            treg(std::string(GEO_FIELDS[f].type) + ":" + complete + "." + GEO_FIELDS[f].name,
+                                 TableSrc{TC_GEOIP, vs, f, GEO_FIELDS[f].kind});
+                        }
                     break;
                 }
                 default:
@@ -1980,6 +2198,21 @@ void Plan::compile_program() {
                 walk(O_TOKEN, it->second, o.type, o.name, false);
             }
         }
+    }
+    // the GeoIP stages' images: the field table of each stage's wanted fields (lp_geoip.h)
+    for (int k = 0; k < P.n_val && device_ok_; ++k) {
+        if (P.val[k].kind != VK_GEOIP) continue;
+        const mmdb::Db& D = *geodb_[P.val[k].src_qname];
+        GeoImage& G = geo_img_[k];
+        G.tree = &D.tree;
+        G.n_records = (uint32_t)D.rec_off.size();
+        G.fields.clear();
+        G.pool.clear();
+        std::map<std::string, uint32_t> pooled;
+        for (int f = 0; f < GF_COUNT; ++f)
+            if ((P.val[k].want >> f) & 1)
+                for (uint32_t r = 0; r < G.n_records; ++r) G.fields.push_back(geo_field(D, D.rec_off[r], f, G.pool, pooled));
+        if (G.pool.size() >= GEO_NULL) { device_ok_ = false; why_ = "GeoIP string pool too large"; }
     }
     // a remapped name whose new type has dissectors but whose values the walk
     // never reached (e.g. a URI part): the replay could not follow it
@@ -2514,6 +2747,33 @@ void Plan::run_phase(Ctx& c, const Instance& in, const std::string& name, const 
                 const int64_t l = k == UQ_EPOCH ? (int64_t)f[0] * 1000 : k == UQ_PROCESSID ? (int64_t)f[2]
                                   : k == UQ_COUNTER ? (int64_t)f[3] : (int64_t)f[4];
                 emit(c, name, ty[k], nm[k], mlong(l));
+            }
+        }
+        return;
+    }
+    case D_GEOIP_COUNTRY: case D_GEOIP_CITY: case D_GEOIP_ASN: case D_GEOIP_ISP: {
+        // AbstractGeoIPDissector.dissect (:93-110) and the classes' extract*Fields: the
+        // record k_geoip_lines found (column geo: its id + 1, 0 when the value is not in the tree), its wanted fields from the stage's field table in delivery
+        // order.  A null field is delivered as null (core/Parsable.java:77-134) except
+        // the three the dissector tests first; a DOUBLE as its Double.toString text.
+        if (v.null || v.is_long || v.len == 0 || ok != O_TOKEN) return;
+        const int vs = val_of_.at(VK_GEOIP | ((in.cls - D_GEOIP_COUNTRY) << 5) | ((t_fmt * 64 + oi) << 8));
+        const GeoImage& G = geo_img_[vs];
+        // (a view without the column -- the test-only emulation's -- looks the value up here, with the kernel's functions)
+        const int64_t found = R.geo[vs] ? (int64_t)R.geo[vs][i] : geo_lookup(v.p, v.len, G.tree->data());
+        if (found <= 0 || found > (int64_t)G.n_records) return;
+        const uint32_t rec = (uint32_t)found;
+        const uint32_t want = (uint32_t)prog_.val[vs].want;
+        for (int f = 0; f < GF_COUNT; ++f) {
+            if (!((want >> f) & 1u) || !has(GEO_FIELDS[f].name)) continue;
+            const GeoField& F = G.fields[(size_t)geo_slot(want, f) * G.n_records + (rec - 1)];
+            set_origin(O_NONE, 0);
+            if (F.off == GEO_NULL) {
+                if (!GEO_FIELDS[f].skip_null) emit(c, name, GEO_FIELDS[f].type, GEO_FIELDS[f].name, mnull());
+            } else if (GEO_FIELDS[f].kind == GK_LONG) {
+                emit(c, name, GEO_FIELDS[f].type, GEO_FIELDS[f].name, mlong((int64_t)F.v));
+            } else {
+                emit(c, name, GEO_FIELDS[f].type, GEO_FIELDS[f].name, mstr((const uint8_t*)G.pool.data() + F.off, F.len));
             }
         }
         return;

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "lp_geoip.h"
 #include "lp_program.h"
 #include "lp_table.h"
 
@@ -45,8 +46,12 @@ enum DisClass {
     D_ROOT, D_TIMESTAMP, D_TIMESTAMP_ISO, D_FIRSTLINE, D_PROTOCOL, D_URI, D_QUERY, D_COOKIES, D_SETCOOKIES,
     D_SETCOOKIE, D_UNIQUEID, D_CLF2NUM, D_NUM2CLF, D_STRFTIME, D_LOCALIZED,
     D_BINIP, D_SECMILLIS, D_MS2US, D_UPSTREAM,  // NGINX additional dissectors
-    D_SCREENRES  // ScreenResolutionDissector: only when registered (Parser.addDissector)
+    D_SCREENRES,  // ScreenResolutionDissector: only when registered (Parser.addDissector)
+    // the GeoIP dissectors (hp/dissectors/geoip), each only when registered with its database
+    D_GEOIP_COUNTRY, D_GEOIP_CITY, D_GEOIP_ASN, D_GEOIP_ISP
 };
+constexpr int N_GEODB = 4;  // one database per GeoIP class
+constexpr bool dis_geoip(int cls) { return cls >= D_GEOIP_COUNTRY && cls <= D_GEOIP_ISP; }
 
 struct Dissector {
     int cls;
@@ -108,6 +113,7 @@ struct ResultView {
     const uint32_t* l_count[MAX_LIST] = {};
     const uint64_t* l_tab[MAX_LIST] = {};
     const uint32_t* bip[MAX_BINIP] = {};
+    const uint32_t* geo[MAX_VAL] = {};    // value stage k (VK_GEOIP): the line's record id + 1, 0 none
     const uint32_t* p_count[MAX_PAIR] = {};
     const uint64_t* p_tab[MAX_PAIR] = {};
     const uint8_t* fmt_id = nullptr;      // multi-format programs: the routed LogFormat per line
@@ -136,9 +142,23 @@ struct Remap {
 // the reference's httpdlog-parser jar that is not registered by default, by
 // class name (simple or fully qualified) with the settings string Hive's
 // "load:" / Pig's "-load:" hands initializeFromSettingsParameter.  Known:
-// ScreenResolutionDissector.
+// ScreenResolutionDissector, and GeoIPCountryDissector / GeoIPCityDissector /
+// GeoIPASNDissector / GeoIPISPDissector (also as
+// nl.basjes.parse.httpdlog.dissectors.geoip.<Class>), whose settings are the
+// path of the MaxMind DB file.
 struct AddDissector {
     std::string name, settings;
+};
+
+namespace mmdb { struct Db; }
+// The images of one VK_GEOIP value stage (lp_geoip.h): its database's tree,
+// and the field table of the stage's wanted fields with its byte pool.  Host
+// memory; a handle uploads them to its device once.
+struct GeoImage {
+    const std::vector<uint64_t>* tree = nullptr;
+    uint32_t n_records = 0;
+    std::vector<GeoField> fields;  // [slot][record id]
+    std::string pool;
 };
 
 class Plan {
@@ -150,7 +170,11 @@ public:
                               std::string& err, const std::vector<Remap>& remaps = {},
                               const std::vector<AddDissector>& dissectors = {});
 
+    Plan();
+    ~Plan();
     const Program& program() const { return prog_; }
+    // the images of value stage k (kind VK_GEOIP)
+    const GeoImage& geo_image(int k) const { return geo_img_[k]; }
     // Parser.getCasts(name) (core/Parser.java:127-129): CAST_* bits of a
     // "TYPE:path" the dissectors deliver for the requested paths, -1 unknown
     int casts(const std::string& target) const;
@@ -222,6 +246,10 @@ private:
     std::map<std::string, std::set<std::string>> remaps_;  // Parser.typeRemappings: input path -> new types
     bool screenres_ = false;            // ScreenResolutionDissector is registered
     std::string screenres_settings_;    // ... its settings: kept, never used (the separator is always "x", lp_value.h screen_split)
+    // the registered GeoIP classes' databases (index = class - D_GEOIP_COUNTRY; null: not registered)
+    std::unique_ptr<mmdb::Db> geodb_[N_GEODB];
+    std::string geodb_path_[N_GEODB];
+    GeoImage geo_img_[MAX_VAL];
     std::map<std::string, int> casts_;  // castsOfTargets
     uint64_t gen_ = 0;                  // this build's id (the replay's per-thread memo)
     std::map<std::string, std::vector<Instance>> compiled_;

@@ -38,7 +38,7 @@ namespace {
 
 constexpr int TB = 256;
 
-template <bool EXT>
+template <bool EXT, bool GEO>
 __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restrict__ args,
                                                      const TableArgs* __restrict__ targs, const uint8_t* buf) {
     const Program& P = args->prog;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restric
         for (int pass = 0; pass < 2 && ok && !valid; ++pass) {
             const TableSrc& sc = pass ? col.alt[fmt] : col.src[fmt];
             if (pass && sc.kind == TC_NONE) break;
-            const TVal v = tvalue(P, C, T, sc, i, line, region);
+            const TVal v = tvalue_any<GEO>(P, C, T, sc, i, line, region);
             valid = v.kind != 0;
             if (col.kind == 1) {  // STRING: its length now, its bytes after the scan
                 x = v.kind == 2 ? digits(v.l) : v.n + (v.amp ? 1u : 0u);
@@ -99,6 +99,8 @@ __global__ __launch_bounds__(TB) void k_table_values(const DeviceArgs* __restric
                 if (v.kind == 1 && sc.kind == TC_LIST) d = decimal_to_double(v.p, v.n);
                 else if (v.kind == 2) d = (double)v.l;
                 else valid = false;
+                if constexpr (GEO)  // a DOUBLE field: its text, the f64's bits in l
+                    if (v.kind == 1 && sc.kind == TC_GEOIP && sc.c == GK_DOUBLE) { d = __longlong_as_double(v.l); valid = true; }
             }
         }
         if (col.kind == 1) {
@@ -479,9 +481,11 @@ int launch_table_values(const DeviceArgs* d_args, const TableArgs* d_targs, cons
     }
     if (table_ext(ta)) {
         if (hipMemsetAsync(ta.bad_row, 0, 4, s) != hipSuccess) return -1;
-        hipLaunchKernelGGL(k_table_values<true>, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+        if (has_geo(ta)) hipLaunchKernelGGL((k_table_values<true, true>), dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+        else hipLaunchKernelGGL((k_table_values<true, false>), dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
     } else {
-        hipLaunchKernelGGL(k_table_values<false>, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+        if (has_geo(ta)) hipLaunchKernelGGL((k_table_values<false, true>), dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
+        else hipLaunchKernelGGL((k_table_values<false, false>), dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, d_args, d_targs, buf);
     }
     if (mid) hipEventRecord(mid, s);  // the values kernel done: the scans follow
     if (!offsets) return hipGetLastError() == hipSuccess ? 0 : -1;  // i64[k + 1] stays row k's length (dict.hip)

@@ -9,6 +9,7 @@
 
 #include "kernels.h"
 #include "lp_device.h"
+#include "lp_geoip.h"  // GeoField, geo_slot (TC_GEOIP)
 #include "lp_value.h"  // digits, write_long, parse_long, decimal_to_double
 
 namespace lp {
@@ -125,9 +126,33 @@ __device__ __noinline__ void remap_value(int tc, int fld, const LP_G uint8_t* sp
                                                                                                           : (int64_t)f[4];
 }
 
+// A GeoIP output (TC_GEOIP): a gather from the stage's field table (lp_geoip.h
+// GeoField as two u64: v; off | len << 32) through the line's record id + 1
+// (rec; 0: a null / empty address, or one that is not in the tree -- no
+// outputs).  A LONG field is its value; a STRING its bytes in the pool; a
+// DOUBLE its text in the pool with the f64's bits in l (for a DOUBLE column).
+// Out of line, as remap_value.  kind / p / n / l as TVal.
+__device__ __noinline__ void geo_value(const Columns& C, int32_t want, const TableSrc& s, int64_t i, int& kind,
+                                       const LP_G uint8_t*& p, uint32_t& n, int64_t& l) {
+    const uint32_t rec = C.geo[s.a][i];
+    if (rec == 0) return;
+    const LP_G uint64_t* f = C.geo_fields[s.a] + 2 * ((size_t)geo_slot((uint32_t)want, s.b) * C.geo_records[s.a] + (rec - 1));
+    const uint64_t w1 = f[1];
+    if ((uint32_t)w1 == GEO_NULL) return;
+    l = (int64_t)f[0];
+    if (s.c == GK_LONG) {
+        kind = 2;
+    } else {
+        kind = 1;
+        p = C.geo_pool[s.a] + (uint32_t)w1;
+        n = (uint32_t)(w1 >> 32);
+    }
+}
+
 __device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, const TableSrc& s, int64_t i,
                        const LP_G uint8_t* line, const LP_G uint8_t* region) {
     TVal v;
+
     auto bytes = [&](const LP_G uint8_t* p, uint32_t n) {
         v.kind = 1;
         v.p = p;
@@ -335,6 +360,32 @@ __device__ TVal tvalue(const Program& P, const Columns& C, const TableArgs& T, c
     default:  // TC_NONE, TC_NULL
         return v;
     }
+}
+
+// tvalue, or (GEO) a GeoIP output.  k_table_values has a GEO instance for
+// tables with a TC_GEOIP source; its other instances compile to the code they
+// were.  A GeoIP value is always a pointer word or a long of at most 62 bits
+// (plan.cpp geo_field), never SW_SLOW: k_table_chars and the dictionary
+// kernels, which derive only SW_SLOW values again, never meet one.  (As one more case of tvalue's switch, or as a test in front of
+// it in the one instance, the GeoIP source changed the compiler's inlining and
+// register allocation of k_table_values and k_dict_insert, which then ran 25 %
+// to 100 % longer on columns that have nothing to do with it.)
+// has_geo: some column of the table has such a source (host).
+inline bool has_geo(const TableArgs& ta) {
+    for (int c = 0; c < ta.n_cols; ++c)
+        for (int f = 0; f < MAX_FMT; ++f)
+            if (ta.cols[c].src[f].kind == TC_GEOIP || ta.cols[c].alt[f].kind == TC_GEOIP) return true;
+    return false;
+}
+template <bool GEO>
+__device__ __forceinline__ TVal tvalue_any(const Program& P, const Columns& C, const TableArgs& T, const TableSrc& s,
+                                           int64_t i, const LP_G uint8_t* line, const LP_G uint8_t* region) {
+    if constexpr (GEO) if (s.kind == TC_GEOIP) {
+        TVal v;
+        geo_value(C, P.val[s.a].want, s, i, v.kind, v.p, v.n, v.l);
+        return v;
+    }
+    return tvalue(P, C, T, s, i, line, region);
 }
 
 // the row's line and arena region (a program without URI stages writes no

@@ -81,9 +81,11 @@ def java_double_to_string(d):
     The digits are those of JDK 19+ (JDK-4511638, shortest round trip).  The
     reference's pinned JDK 8 (FloatingDecimal.dtoa) prints more digits for
     some values (e.g. 8.41E21 as "8.409999999999999E21").  Parity unpinned:
-    no reference test covers it, and no dissector on this path delivers a
-    DOUBLE value (only the out-of-scope GeoIP ones do), so getString of a
-    Double is reached only through a caller's own setter types."""
+    no reference test covers it beyond 52.5 and 5.75.  The GeoIP dissectors'
+    DOUBLE outputs (location.latitude / location.longitude) reach a record as
+    this text, printed by the engine with the same rule (lp_mmdb.h
+    java_double); a DOUBLE setter gets Double.parseDouble of it, the value
+    itself."""
     if math.isnan(d):
         return "NaN"
     if math.isinf(d):
