@@ -292,8 +292,12 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * bitmaps and counts, k_arrow_narrow32), summed over the columns.  [16] is
  * written only for n >= 17: a caller that passes 16 sees what it always saw;
  * [17], for n >= 18, is k_geoip_lines of the last batch (0 for a program
- * without a GeoIP stage; it is part of [4]).
- * Returns the number of values written (at most 18). */
+ * without a GeoIP stage; it is part of [4]); then the last complete
+ * lp_result_select_where with terms on a device view: [18] k_where_eval, [19]
+ * its compaction (k_select_count, the block scan, the host's read of the
+ * count and k_select_write over the predicate's bits).  [18] and [19] are
+ * written only for n >= 20: a caller that passes 18 sees what it always saw.
+ * Returns the number of values written (at most 20). */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -548,6 +552,81 @@ int lp_result_table_map(lp_handle *h, const lp_result *r, int64_t first, int64_t
 #define LP_SEL_FALLBACK (1u << LP_LINE_FALLBACK)
 int lp_result_select(lp_handle *h, const lp_result *r, int64_t first, int64_t count, uint32_t status_mask,
                      int64_t *rows, uint64_t rows_cap, uint64_t *rows_len);
+
+/* lp_result_select_where: lp_result_select with a predicate on the lines'
+ * VALUES -- "status >= 500", "the path starts with /api/", "the user agent
+ * contains bot", "the raw line contains a marker" -- evaluated on the device
+ * without building a column; its row list is what the *_rows calls take.
+ *
+ * Line i of [first, first+count) is selected when its status is in
+ * status_mask AND the predicate holds on the row lp_result_table_rows would
+ * build for line i and the terms' (path, kind) columns.  The value of a term
+ * is exactly that column's value on that row: the last delivery wins (the
+ * earlier one when the later is null); a LONG taken from text is
+ * Long.parseLong of it and null when that fails; a STRING taken from a long is
+ * its decimal text; dates, times, month names and binary IPs are their
+ * formatted text; a raw query string has its leading '&'.  A BAD or FALLBACK
+ * line has only null values -- except in the pseudo-columns, valid for every
+ * line as in the table: "@line" is STRING, "@offset", "@lineno" and "@status"
+ * are LONG.  path is a requested "TYPE:path", a wildcard's member by its full
+ * path, or a pseudo-column; kind (LP_CAST_LONG or LP_CAST_STRING) is the
+ * column type the value is taken as.
+ *
+ * Ops: IS_NULL and EQ for either kind; LT / LE / GT / GE (value <op> lo) and
+ * BETWEEN (lo <= value <= hi; lo > hi matches nothing) for LONG, EQ against
+ * lo; PREFIX / SUFFIX / CONTAINS, and EQ, bytewise against str[0, str_len)
+ * for STRING.  An empty operand: PREFIX, SUFFIX and CONTAINS are true on every
+ * non-null value, EQ on the empty string only (an empty string is not null).
+ *
+ * Two-valued logic -- NOT SQL's three-valued one: a comparison with a null
+ * value is false; IS_NULL is true exactly on null; LP_WHERE_NEGATE, or-ed
+ * into op, flips the term's outcome after that rule, so a negated comparison
+ * is TRUE on null and "is not null" is IS_NULL | NEGATE.  SQL's "<>" (false
+ * on null) is EQ | NEGATE in one group and IS_NULL | NEGATE in another.
+ *
+ * The result is the AND over the groups of the OR over each group's terms
+ * (group: non-decreasing over the array).  n_terms == 0 selects what
+ * lp_result_select selects, by its code.
+ *
+ * Output, size protocol (*rows_len always set; LP_E_NOMEM with nothing
+ * written), window, state, memory-kind checks and their codes: those of
+ * lp_result_select, one implementation.  Additionally LP_E_INVALID: n_terms
+ * outside 0..LP_WHERE_MAX_TERMS (or null terms with n_terms > 0), a null
+ * path, a kind other than LONG / STRING, a kind the path's lp_casts lack or
+ * the wrong one for a pseudo-column, an unknown op or one that does not exist
+ * for the kind, a decreasing group, str_len outside 0..255 or a null str with
+ * str_len > 0, or names and operands that together exceed the device table's
+ * name pool (2048 bytes: the parameter / cookie names of the terms' paths
+ * plus every STRING operand); LP_E_MISSING: a path the handle does not
+ * deliver; on a device view LP_E_UNSUPPORTED: a path the device table does
+ * not derive (lp_result_table's rule), or a handle without a device program.
+ * On a host copy (with the input) the same call evaluates the host replay's
+ * values, those of lp_result_table there, and gives the identical row list.
+ * lp_last_timing [18] / [19]: the last complete device call with terms. */
+#define LP_WHERE_MAX_TERMS 8
+#define LP_WHERE_IS_NULL   0
+#define LP_WHERE_EQ        1
+#define LP_WHERE_LT        2
+#define LP_WHERE_LE        3
+#define LP_WHERE_GT        4
+#define LP_WHERE_GE        5
+#define LP_WHERE_BETWEEN   6
+#define LP_WHERE_PREFIX    7
+#define LP_WHERE_SUFFIX    8
+#define LP_WHERE_CONTAINS  9
+#define LP_WHERE_NEGATE    0x100
+typedef struct lp_where_term {
+    const char *path;
+    int32_t kind;       /* LP_CAST_LONG or LP_CAST_STRING */
+    int32_t op;         /* LP_WHERE_*, LP_WHERE_NEGATE may be or-ed in */
+    int32_t group;      /* terms of one group are OR-ed, the groups AND-ed */
+    int32_t str_len;    /* STRING operand, 0..255 bytes */
+    int64_t lo, hi;     /* LONG operands */
+    const uint8_t *str;
+} lp_where_term;
+int lp_result_select_where(lp_handle *h, const lp_result *r, int64_t first, int64_t count, uint32_t status_mask,
+                           const lp_where_term *terms, int n_terms, int64_t *rows, uint64_t rows_cap,
+                           uint64_t *rows_len);
 
 /* lp_result_table / lp_result_table_map with row k = line rows[k] (batch-
  * relative, as lp_result_select writes them): what the record reader and the

@@ -62,6 +62,104 @@ class LpTableCol(ctypes.Structure):
                 ("chars_cap", ctypes.c_uint64), ("chars_len", ctypes.c_uint64)]
 
 
+class LpWhereTerm(ctypes.Structure):
+    """lp_where_term (include/logparser_amd.h): one term of lp_result_select_where"""
+    _fields_ = [("path", ctypes.c_char_p), ("kind", ctypes.c_int32), ("op", ctypes.c_int32), ("group", ctypes.c_int32),
+                ("str_len", ctypes.c_int32), ("lo", ctypes.c_int64), ("hi", ctypes.c_int64), ("str", ctypes.c_char_p)]
+
+
+# lp_result_select_where's ops (LP_WHERE_*); WHERE_NEGATE may be or-ed in
+(WHERE_IS_NULL, WHERE_EQ, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE, WHERE_BETWEEN, WHERE_PREFIX, WHERE_SUFFIX,
+ WHERE_CONTAINS) = range(10)
+WHERE_NEGATE = 0x100
+WHERE_MAX_TERMS = 8
+_WHERE_LONG_OPS = (WHERE_IS_NULL, WHERE_EQ, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE, WHERE_BETWEEN)
+_WHERE_STRING_OPS = (WHERE_IS_NULL, WHERE_EQ, WHERE_PREFIX, WHERE_SUFFIX, WHERE_CONTAINS)
+
+
+class Where:
+    """One term of BatchResult.select_where_*: `path` (a requested "TYPE:path",
+    a wildcard's member, or a pseudo-column) taken as a column of `kind` (int:
+    BIGINT, str: STRING) against an operand.  kind defaults from the
+    operand's Python type -- int gives int, str / bytes give str -- and is
+    required for WHERE_IS_NULL, which has no operand.  op: WHERE_*; value: the
+    operand (BETWEEN: value <= x <= hi); terms of one group are OR-ed, the
+    groups AND-ed; negate flips the term's outcome (true on null then: the
+    logic is two-valued).  Argument errors raise here, before any engine call."""
+
+    def __init__(self, path, op, value=None, hi=None, kind=None, group=0, negate=False):
+        if not isinstance(path, str) or not path:
+            raise ValueError("Where: path must be a non-empty str")
+        if op not in range(10):
+            raise ValueError("Where: unknown op %r" % (op,))
+        if isinstance(value, bool) or isinstance(hi, bool):
+            raise TypeError("Where: a bool is no operand")
+        if kind is None:
+            if isinstance(value, int):
+                kind = int
+            elif isinstance(value, (str, bytes)):
+                kind = str
+            else:
+                raise ValueError("Where: kind is required when the operand does not give it (IS_NULL)")
+        if kind not in (int, str):
+            raise ValueError("Where: kind must be int or str")
+        if op not in (_WHERE_LONG_OPS if kind is int else _WHERE_STRING_OPS):
+            raise ValueError("Where: op %d does not exist for a %s column" % (op, "BIGINT" if kind is int else "STRING"))
+        if op == WHERE_IS_NULL:
+            if value is not None or hi is not None:
+                raise ValueError("Where: IS_NULL takes no operand")
+        elif kind is int:
+            if not isinstance(value, int) or (op == WHERE_BETWEEN) != (hi is not None) or \
+                    (hi is not None and not isinstance(hi, int)):
+                raise ValueError("Where: a BIGINT op takes an int (BETWEEN: value and hi)")
+            for x in (value, hi or 0):
+                if not -(1 << 63) <= x < (1 << 63):
+                    raise ValueError("Where: operand outside int64")
+        else:
+            if not isinstance(value, (str, bytes)) or hi is not None:
+                raise ValueError("Where: a STRING op takes one str / bytes operand")
+            value = value.encode("utf-8") if isinstance(value, str) else bytes(value)
+            if len(value) > 255:
+                raise ValueError("Where: a STRING operand has at most 255 bytes")
+        if not isinstance(group, int) or group < 0:
+            raise ValueError("Where: group must be an int >= 0")
+        self.path, self.op, self.value, self.hi, self.kind, self.group, self.negate = (path, op, value, hi, kind, group,
+                                                                                       bool(negate))
+
+    def __repr__(self):
+        return "Where(%r, %d, %r, hi=%r, kind=%s, group=%d, negate=%r)" % (self.path, self.op, self.value, self.hi,
+                                                                            self.kind.__name__, self.group, self.negate)
+
+
+def _where_array(terms):
+    """(lp_where_term array or None, n, what must stay alive) of a list of Where"""
+    terms = list(terms)
+    if len(terms) > WHERE_MAX_TERMS:
+        raise ValueError("at most %d terms" % WHERE_MAX_TERMS)
+    if any(not isinstance(t, Where) for t in terms):
+        raise TypeError("terms: Where objects expected")
+    if any(a.group > b.group for a, b in zip(terms, terms[1:])):
+        raise ValueError("terms: group must not decrease")
+    if not terms:
+        return None, 0, []
+    arr = (LpWhereTerm * len(terms))()
+    keep = []
+    for k, t in enumerate(terms):
+        w = arr[k]
+        w.path = t.path.encode()
+        w.kind = CAST_LONG if t.kind is int else CAST_STRING
+        w.op = t.op | (WHERE_NEGATE if t.negate else 0)
+        w.group = t.group
+        if t.kind is int:
+            w.lo, w.hi = t.value or 0, t.hi or 0
+        elif t.value is not None:
+            buf = ctypes.create_string_buffer(t.value, len(t.value) + 1)  # (operands may hold NUL bytes)
+            keep.append(buf)
+            w.str = ctypes.cast(buf, ctypes.c_char_p)
+            w.str_len = len(t.value)
+    return arr, len(terms), keep
+
+
 class LpTableMapCol(ctypes.Structure):
     """lp_table_map_col (include/logparser_amd.h): one Arrow map<string,string> column"""
     _fields_ = [("path", ctypes.c_char_p), ("valid", ctypes.c_void_p), ("entry_off", ctypes.c_void_p),
@@ -194,6 +292,9 @@ class EngineUnavailable(RuntimeError):
 # What a table call's code other than LP_OK raises, per family: code -> (exception, message);
 # None: every other code (its message takes the code)
 _SELECT_ERRORS = {None: (ValueError, "lp_result_select failed: %d")}
+_WHERE_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a term's values are derived on the host only: use select_where_from"),
+                 LP_E_MISSING: (MissingDissectorsException, "lp_result_select_where: a path the parser does not deliver"),
+                 None: (ValueError, "lp_result_select_where failed: %d")}
 _TABLE_FROM_ERRORS = {None: (ValueError, "lp_result_table failed: %d")}
 _TABLE_DEVICE_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use table_from"),
                         None: (ValueError, "lp_result_table (device) failed: %d")}
@@ -295,6 +396,10 @@ def lib():
     L.lp_result_select.restype = ctypes.c_int
     L.lp_result_select.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.lp_result_select_where.restype = ctypes.c_int
+    L.lp_result_select_where.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_uint32, ctypes.POINTER(LpWhereTerm), ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.lp_result_table_rows.restype = ctypes.c_int
     L.lp_result_table_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(LpTableCol), ctypes.c_int, ctypes.c_int]
@@ -734,6 +839,44 @@ class BatchResult:
     def select_timing(self):
         """HIP-event ms of the last device lp_result_select (both passes, the scan, the host's read of the count)"""
         return self._timing(11, 12)[0]
+
+    def _select_where(self, res, terms, mask, first, count, alloc, ptr):
+        """lp_result_select_where with the table's size protocol: one call
+        that reports the count, one that fills"""
+        arr, n_terms, keep = _where_array(terms)
+        count = self.n_lines - first if count is None else count
+        L = lib()
+        n = ctypes.c_uint64(0)
+        got = []  # the rows, once the count is known
+
+        def call():
+            return L.lp_result_select_where(self._p._h, ctypes.byref(res), first, count, mask, arr, n_terms,
+                                            ptr(got[0]) if got else None, n.value if got else 0, ctypes.byref(n))
+        _sized_call(call, lambda: got.append(alloc(int(n.value))), _WHERE_ERRORS)
+        del keep
+        return got[0] if got else alloc(0)
+
+    def select_where_device(self, terms, mask=SEL_OK, first=0, count=None):
+        """lp_result_select_where on the device view: the lines of [first,
+        first+count) whose status is in mask and on whose table row the
+        predicate of terms (a list of Where: AND over the groups of OR over a
+        group's terms) holds, ascending, as a torch int64 tensor on the
+        handle's device -- the rows= of table_device.  The predicate runs in
+        one kernel over the parse columns; no column is built."""
+        import torch
+        dev = torch.device("cuda", self._p.device)
+        return self._select_where(self._view(), terms, mask, first, count,
+                                  lambda n: torch.empty(n, dtype=torch.int64, device=dev), lambda t: t.data_ptr())
+
+    def select_where_from(self, res, terms, mask=SEL_OK, first=0, count=None):
+        """lp_result_select_where from a host copy (with the input): a numpy int64 array, the same rows"""
+        return self._select_where(res, terms, mask, first, count, lambda n: np.empty(n, dtype=np.int64),
+                                  lambda a: a.ctypes.data)
+
+    def select_where_timing(self):
+        """HIP-event ms of the last device lp_result_select_where with terms: (the predicate kernel, the
+        compaction: both passes, the scan, the host's read of the count)"""
+        return tuple(self._timing(18, 20))
 
     def table_from(self, res, columns, first=0, count=None, threads=16, decode=True, rows=None):
         """lp_result_table: typed columns of rows [first, first+count) from a

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "lp_arrow.h"
 #include "lp_fixed.h"
+#include "lp_pred.h"
 #include "plan.h"
 
 #if defined(LP_PROFILE)
@@ -127,7 +128,7 @@ bool read_back(hipStream_t s, V* dst, const void* src) {
 }
 
 // where each family's phases start in lp_handle::tms (lp_last_timing index - 5)
-enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7, TMS_ARROW = 11 };
+enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7, TMS_ARROW = 11, TMS_WHERE = 12 };
 
 }  // namespace
 
@@ -170,8 +171,9 @@ struct lp_handle {
     // lp_last_timing [5..16], each family's last successful device call: the table's values / scans /
     // bytes phases; the map columns' count / entries / fill phases, summed over the columns;
     // lp_result_select's passes and scan; the dictionary columns' four phases, summed over the columns;
-    // [16] lp_result_arrow's packaging kernels
-    float tms[12]{};
+    // [16] lp_result_arrow's packaging kernels; ([17]: geo_ms;) [18..19] lp_result_select_where's
+    // predicate kernel and compaction
+    float tms[14]{};
     int dict_hash_bits = 0;  // LP_OPT_DICT_HASH_BITS (tests: 0 = the whole hash)
     bool have_events = false;
     uint64_t counters[4]{};
@@ -1023,7 +1025,10 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     out[16] = h->tms[TMS_ARROW];
     if (n < 18) return 17;
     out[17] = h->geo_ms;
-    return 18;
+    if (n < 20) return 18;  // (a caller of the 18 values sees what it always saw)
+    out[18] = h->tms[TMS_WHERE];
+    out[19] = h->tms[TMS_WHERE + 1];
+    return 20;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -1856,54 +1861,226 @@ int lp_result_table_map_rows(lp_handle* h, const lp_result* r, const int64_t* ro
     return rows_arg(rows, n_rows) ? table_map_any(h, r, 0, n_rows, rows, cols, n_cols, threads) : LP_E_INVALID;
 }
 
-// The lines of a window whose status is in status_mask, ascending (select.hip on
-// a device view; a loop over the copied status column on a host copy)
-int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask, int64_t* rows,
-                     uint64_t rows_cap, uint64_t* rows_len) {
+// ---- row selection: lp_result_select and lp_result_select_where, one implementation
+namespace {
+// a term's value on a host copy, as table_value leaves it in the term's column: 0 null, 1 bytes, 2 a long
+struct WhereVal {
+    int kind = 0;
+    std::string s;
+    int64_t l = 0;
+};
+struct WhereCtx {
+    const std::unordered_map<std::string, std::vector<int>>* by_path;
+    const lp_where_term* terms;
+    WhereVal* vals;
+};
+// ParsedRecord.set as table_value does it: a null is ignored, the last value wins; a LONG column keeps
+// its earlier value when the later one does not parse
+void where_value(void* vctx, const std::string& target, const lp::MVal& v) {
+    WhereCtx& w = *(WhereCtx*)vctx;
+    auto it = w.by_path->find(target);
+    if (it == w.by_path->end() || v.null) return;
+    for (int t : it->second) {
+        WhereVal& x = w.vals[t];
+        if (v.is_long) {
+            x.kind = 2;
+            x.l = v.l;
+        } else if (w.terms[t].kind == LP_CAST_STRING) {
+            x.kind = 1;
+            x.s.assign((const char*)v.p, v.len);
+        } else if (java_parse_long(v.p, v.len, x.l)) {
+            x.kind = 2;
+        }
+    }
+}
+// the term's rule (lp_pred.h) on such a value
+bool where_term(const lp_where_term& t, const WhereVal& x) {
+    if (t.kind == LP_CAST_LONG) return lp::pred_term_long(t.op, x.kind == 0, x.l, t.lo, t.hi);
+    if (x.kind == 2) {  // a STRING taken from a long: its decimal text
+        char b[20];
+        const uint32_t n = lp::digits(x.l);
+        lp::write_long(b, x.l, n);
+        lp::PredLocal v{b, n};
+        return lp::pred_term_bytes(t.op, false, v, t.str, (uint32_t)t.str_len);
+    }
+    lp::PredBytes<const uint8_t*> v{(const uint8_t*)x.s.data(), (uint32_t)x.s.size(), false};
+    return lp::pred_term_bytes(t.op, x.kind == 0, v, t.str, (uint32_t)t.str_len);
+}
+}  // namespace
+
+// The terms of a lp_result_select_where call, in both modes: pseudo[t] the
+// term's TC_* kind when its path is a pseudo-column
+static int check_terms(lp_handle* h, const lp_where_term* terms, int n_terms, std::vector<int>& pseudo) {
+    if (n_terms < 0 || n_terms > LP_WHERE_MAX_TERMS || (n_terms > 0 && !terms)) return LP_E_INVALID;
+    pseudo.assign((size_t)n_terms, 0);
+    for (int t = 0; t < n_terms; ++t) {
+        const lp_where_term& W = terms[t];
+        if (!W.path || (W.kind != LP_CAST_STRING && W.kind != LP_CAST_LONG)) return LP_E_INVALID;
+        if (!lp::pred_op_ok(W.op, W.kind == LP_CAST_STRING ? 1 : 2)) return LP_E_INVALID;
+        if (t > 0 && W.group < terms[t - 1].group) return LP_E_INVALID;
+        if (W.str_len < 0 || W.str_len > lp::PRED_MAX_STR || (W.str_len > 0 && !W.str)) return LP_E_INVALID;
+        if (const int st = check_path(h, W.path, W.kind, &pseudo[t])) return st;
+    }
+    return LP_OK;
+}
+
+// The terms bound for k_where_eval: column t of ta is term t's (Plan::table_src),
+// the STRING operands follow the names in ta's pool
+static int bind_terms(lp_handle* h, const lp_where_term* terms, int n_terms, lp::TableArgs& ta, lp::WhereArgs& wa) {
+    std::string names;
+    size_t operands = 0;
+    for (int t = 0; t < n_terms; ++t) operands += terms[t].kind == LP_CAST_STRING ? (size_t)terms[t].str_len : 0;
+    for (int t = 0; t < n_terms; ++t) {
+        lp::TableCol& T = ta.cols[t];
+        T.kind = terms[t].kind;
+        const std::string path = terms[t].path;
+        if (!h->plan.table_src(path, T.src, names, T.alt))  // (false also when the names pool is full)
+            return names.size() + path.size() + operands > (size_t)lp::TABLE_NAMES ? LP_E_INVALID : LP_E_UNSUPPORTED;
+    }
+    if (names.size() + operands > (size_t)lp::TABLE_NAMES) return LP_E_INVALID;
+    for (int t = 0; t < n_terms; ++t) {
+        lp::WhereTerm& R = wa.t[t];
+        R.op = terms[t].op;
+        R.group = terms[t].group;
+        R.lo = terms[t].lo;
+        R.hi = terms[t].hi;
+        R.str_off = (int32_t)names.size();
+        R.str_len = terms[t].kind == LP_CAST_STRING ? terms[t].str_len : 0;
+        if (R.str_len > 0) names.append((const char*)terms[t].str, (size_t)R.str_len);
+    }
+    memcpy(ta.names, names.data(), names.size());
+    wa.n_terms = n_terms;
+    return LP_OK;
+}
+
+// The lines of a window whose status is in status_mask -- and on which the
+// terms' predicate holds -- ascending.  A device view: select.hip's stream
+// compaction of the status column, or (terms) of the bits where.hip's
+// k_where_eval leaves; a host copy: a loop over the copied status column and
+// (terms) the host replay's values.
+static int select_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask,
+                      const lp_where_term* terms, int n_terms, int64_t* rows, uint64_t rows_cap, uint64_t* rows_len) {
     if (!h || !r || !rows_len) return LP_E_INVALID;
     if (status_mask & ~(uint32_t)(LP_SEL_OK | LP_SEL_BAD | LP_SEL_FALLBACK)) return LP_E_INVALID;
     *rows_len = 0;
+    std::vector<int> pseudo;
+    if (const int st = check_terms(h, terms, n_terms, pseudo)) return st;
     if (!r->on_host) {
         if (!view_current(h, r) || ensure_synced(h) != LP_OK) return LP_E_STATE;
         if (!check_window(first, count, nullptr, h->n_lines)) return LP_E_INVALID;
         if (rows_cap && !device_memory(h, rows)) return LP_E_INVALID;
+        std::unique_ptr<lp::TableArgs> ta;
+        lp::WhereArgs wa{};
+        if (n_terms > 0) {
+            ta = table_args(h, 0, 0, nullptr, n_terms);
+            if (const int st = bind_terms(h, terms, n_terms, *ta, wa)) return st;
+        }
         if (count == 0 || status_mask == 0) return LP_OK;
         hipSetDevice(h->device);
         hipStream_t s = h->stream;
         if (!h->tscratch.ensure(lp::select_scratch_bytes(first, count))) return LP_E_NOMEM;
+        const bool where = n_terms > 0;
+        PhaseTimer T{h->tev, s};  // start, (terms: the predicate kernel done,) end of the compaction
+        if (where) {
+            if (!h->targs.ensure(sizeof(lp::TableArgs))) return LP_E_NOMEM;
+            if (hipMemcpyAsync(h->targs.p, ta.get(), sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess)
+                return LP_E_DEVICE;
+            wa.first = first;
+            wa.count = count;
+            wa.mask = status_mask;
+            wa.bits = lp::select_bits(first, count, h->tscratch.p, h->tscratch.cap);
+            T.mark(2);
+            if (lp::launch_where_eval(h->args.as<lp::DeviceArgs>(), h->targs.as<lp::TableArgs>(), *ta, h->d_buf, wa, s) != 0)
+                return LP_E_DEVICE;
+        }
         const int64_t* d_total = nullptr;
         int64_t total = 0;
-        PhaseTimer T{h->tev, s};  // start, end of its kernels
         T.mark(0);
-        if (lp::launch_select_count(h->C.status, first, count, status_mask, h->tscratch.p, h->tscratch.cap, s, &d_total) != 0)
+        if (lp::launch_select_count(h->C.status, first, count, status_mask, h->tscratch.p, h->tscratch.cap, s, &d_total,
+                                    where) != 0)
             return LP_E_DEVICE;
         // the number of selected lines decides whether they fit
         if (!read_back(s, &total, d_total)) return LP_E_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         *rows_len = (uint64_t)total;
         if ((uint64_t)total > rows_cap) return LP_E_NOMEM;
-        if (total > 0 &&
-            lp::launch_select_write(h->C.status, first, count, status_mask, rows, h->tscratch.p, h->tscratch.cap, s) != 0)
+        if (total > 0 && lp::launch_select_write(h->C.status, first, count, status_mask, rows, h->tscratch.p,
+                                                 h->tscratch.cap, s, where) != 0)
             return LP_E_DEVICE;
         T.mark(1);
         if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
         // (the host's read of the total between the passes is inside the interval)
-        h->tms[TMS_SELECT] = T.elapsed(0, 1);
+        if (where) {
+            h->tms[TMS_WHERE] = T.elapsed(2, 0);
+            h->tms[TMS_WHERE + 1] = T.elapsed(0, 1);
+        } else {
+            h->tms[TMS_SELECT] = T.elapsed(0, 1);
+        }
         return LP_OK;
+    }
+    if (n_terms > 0 && !r->input) return LP_E_INVALID;  // (the values are read from the copied input)
+    if (n_terms > 0) {  // the names pool's bound holds in both modes (what only the device refuses does not)
+        auto ta = table_args(h, 0, 0, nullptr, n_terms);
+        lp::WhereArgs wa{};
+        if (bind_terms(h, terms, n_terms, *ta, wa) == LP_E_INVALID) return LP_E_INVALID;
     }
     if (!check_window(first, count, nullptr, r->n_lines)) return LP_E_INVALID;
     lp::ResultView V;
     make_view(h, *r, V);
     if (!V.status && count > 0) return LP_E_INVALID;
-    auto selected = [&](int64_t i) { return ((status_mask >> (V.status[i] & 7u)) & 1u) != 0; };
-    uint64_t n = 0;
-    for (int64_t i = first; i < first + count; ++i) n += selected(i) ? 1 : 0;
-    *rows_len = n;
-    if (n > rows_cap || (n && !rows)) return LP_E_NOMEM;  // (nothing written)
-    n = 0;
+    std::unordered_map<std::string, std::vector<int>> by_path;
+    for (int t = 0; t < n_terms; ++t)
+        if (!pseudo[t]) by_path[terms[t].path].push_back(t);
+    std::vector<WhereVal> vals((size_t)n_terms);
+    auto selected = [&](int64_t i) {
+        const uint32_t st = V.status[i];
+        if (((status_mask >> (st & 7u)) & 1u) == 0) return false;
+        if (n_terms == 0) return true;
+        for (auto& x : vals) x.kind = 0;
+        if (st == LP_LINE_OK && !by_path.empty()) {
+            WhereCtx ctx{&by_path, terms, vals.data()};
+            h->plan.rec_row(V, i, where_value, &ctx);
+        }
+        lp::PredFold F;
+        for (int t = 0; t < n_terms; ++t) {
+            lp::pred_fold_group(F, t, terms[t].group);
+            if (!lp::pred_fold_wants(F)) continue;
+            bool out;
+            if (pseudo[t] == lp::TC_LINE) {  // the line as the parse kernels see it (kernels_common.h crlf_len)
+                const uint64_t s0 = V.line_off[i];
+                uint64_t n = V.line_off[i + 1] - 1 - s0;
+                if (n > 0 && V.input[s0 + n - 1] == '\r') --n;
+                lp::PredBytes<const uint8_t*> v{V.input + s0, (uint32_t)n, false};
+                out = lp::pred_term_bytes(terms[t].op, false, v, terms[t].str, (uint32_t)terms[t].str_len);
+            } else if (pseudo[t]) {
+                const int64_t x = pseudo[t] == lp::TC_OFFSET ? (int64_t)V.line_off[i]
+                                  : pseudo[t] == lp::TC_LINENO ? r->first_line + i : (int64_t)st;
+                out = lp::pred_term_long(terms[t].op, false, x, terms[t].lo, terms[t].hi);
+            } else {
+                out = where_term(terms[t], vals[(size_t)t]);
+            }
+            lp::pred_fold_term(F, out);
+        }
+        return lp::pred_fold_result(F, n_terms);
+    };
+    // (one evaluation per line: the matches, then whether they fit)
+    std::vector<int64_t> got;
     for (int64_t i = first; i < first + count; ++i)
-        if (selected(i)) rows[n++] = i;
+        if (selected(i)) got.push_back(i);
+    *rows_len = (uint64_t)got.size();
+    if (got.size() > rows_cap || (!got.empty() && !rows)) return LP_E_NOMEM;  // (nothing written)
+    if (!got.empty()) memcpy(rows, got.data(), 8 * got.size());
     return LP_OK;
+}
+
+int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask, int64_t* rows,
+                     uint64_t rows_cap, uint64_t* rows_len) {
+    return select_any(h, r, first, count, status_mask, nullptr, 0, rows, rows_cap, rows_len);
+}
+
+int lp_result_select_where(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask,
+                           const lp_where_term* terms, int n_terms, int64_t* rows, uint64_t rows_cap, uint64_t* rows_len) {
+    return select_any(h, r, first, count, status_mask, terms, n_terms, rows, rows_cap, rows_len);
 }
 
 // ---- Arrow C Data Interface export (arrow_export.cpp, lp_arrow.h)

@@ -175,13 +175,23 @@ int launch_dict_index(const TableArgs& ta, const DictArgs& da, hipStream_t s);
 //   launch_select_count  the blocks' match counts and their scan; *total: the
 //                        device word that will hold the number of matches
 //   launch_select_write  (the total fits rows) the indices
+// from_bits (lp_result_select_where): both passes take their match words from
+// the scratch's bit words -- select_bits(), one per 64 lines counted from first
+// rounded down to 16, which launch_where_eval filled (where.hip; lp_table.h
+// WhereArgs) -- instead of from status and mask.
 constexpr int SEL_WAVE_LINES = 1024;
 constexpr int SEL_BLOCK_LINES = 4096;
 size_t select_scratch_bytes(int64_t first, int64_t count);
+uint64_t* select_bits(int64_t first, int64_t count, void* scratch, size_t scratch_bytes);  // null: the scratch is short
 int launch_select_count(const uint8_t* status, int64_t first, int64_t count, uint32_t mask, void* scratch,
-                        size_t scratch_bytes, hipStream_t s, const int64_t** total);
+                        size_t scratch_bytes, hipStream_t s, const int64_t** total, bool from_bits = false);
 int launch_select_write(const uint8_t* status, int64_t first, int64_t count, uint32_t mask, int64_t* rows, void* scratch,
-                        size_t scratch_bytes, hipStream_t s);
+                        size_t scratch_bytes, hipStream_t s, bool from_bits = false);
+// k_where_eval: the predicate of wa over the lines [wa.first, wa.first + wa.count)
+// (count > 0), term t's value the column ta.cols[t] (d_targs: ta on the device),
+// one bit per line into wa.bits
+int launch_where_eval(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
+                      const WhereArgs& wa, hipStream_t s);
 
 // The Arrow export's packaging on device memory (arrow.hip).
 //   launch_arrow_validity  n_cols columns' valid bytes [n_rows] (n_rows > 0; any

@@ -149,4 +149,27 @@ struct DictArgs {
     LP_G int64_t* reps;
 };
 
+// ---- lp_result_select_where on a device view (where.hip): term t's value is
+// column t of a TableArgs without output pointers (its src / alt per LogFormat,
+// its kind 1 STRING / 2 LONG, the names pool; rows null, n_lines / first_line
+// set); its rule travels here, by value.  A STRING operand is
+// TableArgs::names[str_off, str_off + str_len), after the columns' names.
+// bits: one word per 64 lines counted from first rounded down to 16 -- the
+// lines of select.hip's 16-line groups -- bit b of word w set when line (first
+// & ~15) + 64 w + b is selected; every word that holds a line of the window is
+// written whole.
+constexpr int WHERE_MAX_TERMS = 8;
+struct WhereTerm {
+    int32_t op, group;  // lp_pred.h PRED_* (| PRED_NEGATE); terms of one group are OR-ed, the groups AND-ed
+    int32_t str_off, str_len;
+    int64_t lo, hi;
+};
+struct WhereArgs {
+    int64_t first, count;
+    int32_t n_terms;
+    uint32_t mask;  // the status mask
+    LP_G uint64_t* bits;
+    WhereTerm t[WHERE_MAX_TERMS];
+};
+
 }  // namespace lp
