@@ -202,7 +202,17 @@ int64_t lp_possible_paths_dissectors(const char *logformats, int max_depth, cons
 #define LP_OPT_DICT_HASH_BITS 8 /* tests: lp_result_table_dict on a device view keeps only this many low
                                   bits of a value's hash for its home slot (1..32; 0 = default, all 64
                                   bits): distinct values then collide, and a few hundred rows run the
-                                  probe and byte-compare paths.  The result does not depend on it */
+                                  probe and byte-compare paths.  The result does not depend on it.
+                                  lp_result_group on a device view narrows its key hash the same way,
+                                  the home slot and the hash it stores per row: distinct key tuples
+                                  then meet in the probe and in the full compare */
+#define LP_OPT_GROUP_LDS_WORDS 9 /* tests, measurements: lp_result_group on a device view accumulates in
+                                  per-block LDS copies when groups x accumulator words per group is at
+                                  most this many 8-byte words, else with global atomics (1..8192; 0 =
+                                  default 4096; -1: never in LDS).  The result does not depend on it */
+#define LP_OPT_GROUP_PEEL 10   /* measurements: rounds in which a wave of lp_result_group's global-
+                                  atomic regime merges the rows of its leading group into one atomic
+                                  (1..4; 0 = default 2; -1: none).  The result does not depend on it */
 int lp_set_option(lp_handle *h, int option, int64_t value);
 
 /* Capacity for the coming batches: columns for max_lines lines and at least
@@ -296,8 +306,12 @@ int lp_counters(lp_handle *h, uint64_t *out, int n);
  * lp_result_select_where with terms on a device view: [18] k_where_eval, [19]
  * its compaction (k_select_count, the block scan, the host's read of the
  * count and k_select_write over the predicate's bits).  [18] and [19] are
- * written only for n >= 20: a caller that passes 18 sees what it always saw.
- * Returns the number of values written (at most 20). */
+ * written only for n >= 20: a caller that passes 18 sees what it always saw;
+ * then the last complete lp_result_group on a device view: [20] the resets and
+ * k_group_insert (the keys' values, their hash, the insert), [21] k_dict_mark,
+ * the rank scan and k_dict_index (the groups' numbers), [22] the accumulators'
+ * fill, k_group_agg and k_group_finish.  [20..22] are written only for n >= 23.
+ * Returns the number of values written (at most 23). */
 int lp_last_timing(lp_handle *h, float *out_ms, int n);
 
 /* Run histograms of the last batch, computed on the device (SURVEY.md §5
@@ -721,6 +735,97 @@ int lp_result_table_dict(lp_handle *h, const lp_result *r, int64_t first, int64_
                          int n_cols, int threads);
 int lp_result_table_dict_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
                               lp_table_dict_col *cols, int n_cols, int threads);
+
+/* ---- Grouped aggregates (GROUP BY) over the rows of a batch. ----
+ * What the reference's users run on top of the parser is a query over log
+ * lines: the Hive SerDe hands Hive one row per line (httpdlog-serde/.../
+ * ApacheHttpdlogDeserializer.java:284-323), the record reader one ParsedRecord
+ * (ApacheHttpdLogfileRecordReader.java:246-287), the Pig loader one tuple
+ * (httpdlog-pigloader/.../Loader.java:227-229), and after WHERE nearly every
+ * such query ends in GROUP BY: hits and bytes per status, top paths, requests
+ * per client or per hour.  These calls answer it from the parsed batch: the
+ * groups of up to LP_GROUP_MAX_KEYS key columns and up to LP_GROUP_MAX_AGGS
+ * aggregates of LONG measures per group, without building a key or measure
+ * column -- a handful of rows out instead of 12 bytes per row and an
+ * aggregation elsewhere.
+ *
+ * Rows: those of lp_result_table (first, count) / lp_result_table_rows (rows,
+ * n_rows: any order, repeats allowed; lp_result_select_where's output goes
+ * straight in).  The value of a key or a measure on row k is exactly what
+ * lp_result_table_rows builds for its (path, kind): the last delivery wins,
+ * a LONG from text is Long.parseLong or null, dates and times are their
+ * formatted text, CLF2NUM gives 0 for "-", and the pseudo-columns "@line" /
+ * "@offset" / "@lineno" / "@status" are valid for every status while a BAD or
+ * FALLBACK line is null in every real column.  Measures are LONG (a DOUBLE
+ * sum would depend on the order of arrival).
+ *
+ * Keys: two rows are in one group when every key agrees -- both null, or both
+ * non-null and equal: by int64 value for a LONG key ("007" and "7" are one
+ * group), by bytes for a STRING key (they are two).  Null is a key value of
+ * its own, distinct from "".  n_keys == 0: one group of every row (none when
+ * count is 0).
+ *
+ * Output: groups are numbered by FIRST OCCURRENCE over the call's row index k,
+ * as dictionary entries are.  rep[g] is the batch-relative line of group g's
+ * first row: lp_result_table_rows(rep) gives the key values; no key bytes are
+ * written here.  group_of[k] (optional) is row k's group.  Aggregate a writes
+ * value[g] / valid[g]: COUNT_ROWS and COUNT are always valid; SUM (two's-
+ * complement wrap, Java's long +), MIN and MAX of the non-null values are
+ * valid 0, value 0, for a group without one.  Every result is independent of
+ * the order the rows are taken in, so a device view and a host copy give
+ * byte-identical rep, group_of, value and valid.
+ * Sizes: rep and every value / valid have groups_cap entries; n_groups is
+ * always set and exact; groups_cap < n_groups returns LP_E_NOMEM with rep,
+ * value and valid untouched (group_of is unspecified then): call again.
+ * count 0: LP_OK, n_groups 0.
+ * Errors: those of lp_result_table / lp_result_table_rows through the same
+ * checks (LP_E_MISSING, LP_E_UNSUPPORTED on a device view for a path the
+ * device table does not derive, LP_E_STATE, a row index outside the batch);
+ * LP_E_INVALID additionally for n_keys outside 0..LP_GROUP_MAX_KEYS or n_aggs
+ * outside 0..LP_GROUP_MAX_AGGS, a null array with a count above 0, a null
+ * path where one is needed or a path on COUNT_ROWS, a key kind other than
+ * LONG / STRING or one the path's lp_casts lack, a measure whose lp_casts lack
+ * LONG, an unknown op, a null value / valid or rep with groups_cap > 0, a
+ * negative groups_cap, names that exceed the device table's pool, and count
+ * above 2^31 - 1.  On a device view every pointer and the row list are memory
+ * of the handle's device (anything else: LP_E_INVALID, nothing dereferenced),
+ * and the groups are built in HBM: the dictionary's lock-free insert on a
+ * hash of the key tuple, then an accumulation in per-block LDS copies (few
+ * groups) or with global atomics after a wave-level merge of the leading
+ * groups; LP_E_DEVICE if the hash table overflowed (it
+ * cannot: it has two slots per row).  On a host copy (with the input) they are
+ * built from the host table's columns and a hash map in row order, `threads`
+ * as in lp_result_table.  Groups of several batches or GPUs are merged by the
+ * caller, by key value, on these few rows.
+ * lp_last_timing [20..22]: the last complete device call's phases. */
+#define LP_GROUP_MAX_KEYS 4
+#define LP_GROUP_MAX_AGGS 8
+#define LP_AGG_COUNT_ROWS 0   /* path NULL: the group's rows */
+#define LP_AGG_COUNT      1   /* rows on which the path's LONG value is not null */
+#define LP_AGG_SUM        2   /* of the non-null values, two's-complement wrap (Java long +) */
+#define LP_AGG_MIN        3
+#define LP_AGG_MAX        4
+typedef struct lp_group_key {
+    const char *path;
+    int32_t kind;        /* LP_CAST_LONG or LP_CAST_STRING */
+} lp_group_key;
+typedef struct lp_group_agg {
+    const char *path;    /* NULL for LP_AGG_COUNT_ROWS */
+    int32_t op;          /* LP_AGG_* */
+    int64_t *value;      /* [groups_cap] */
+    uint8_t *valid;      /* [groups_cap] */
+} lp_group_agg;
+typedef struct lp_group_out {
+    int64_t *rep;        /* [groups_cap] batch-relative line of the group's first row */
+    int32_t *group_of;   /* [count] group of row k; may be NULL */
+    int64_t  groups_cap; /* in */
+    int64_t  n_groups;   /* out, always set */
+} lp_group_out;
+int lp_result_group(lp_handle *h, const lp_result *r, int64_t first, int64_t count, const lp_group_key *keys,
+                    int n_keys, const lp_group_agg *aggs, int n_aggs, lp_group_out *out, int threads);
+int lp_result_group_rows(lp_handle *h, const lp_result *r, const int64_t *rows, int64_t n_rows,
+                         const lp_group_key *keys, int n_keys, const lp_group_agg *aggs, int n_aggs,
+                         lp_group_out *out, int threads);
 
 /* ---- Arrow C Data Interface export of the typed, dictionary and map columns. ----
  * One call turns rows of a batch into an Arrow record batch that any Arrow

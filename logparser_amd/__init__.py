@@ -36,6 +36,8 @@ BUF_HOST, BUF_DEVICE = 0, 1
 OPT_FORCE_DIRECT, OPT_MAX_RETRIES, OPT_ARENA_BYTES, OPT_CHUNK_LINES, OPT_CHUNK_WAIT, OPT_ONE_PASS = 1, 2, 3, 4, 5, 6
 OPT_FIXED_SHAPE = 7  # 0: never the chunk kernel's fixed-shape instances (default 1)
 OPT_DICT_HASH_BITS = 8  # tests: low bits of a value's hash the device dictionary keeps for its home slot (0: all)
+OPT_GROUP_LDS_WORDS = 9  # tests, measurements: LDS budget (8-byte words) of the device group call's privatised regime (0: default, -1: none)
+OPT_GROUP_PEEL = 10  # measurements: peel rounds of its global-atomic regime (0: default, -1: none)
 ARENA_SHARDS = 64
 # lp_result_select's status mask (1 << LINE_*)
 SEL_OK, SEL_BAD, SEL_FALLBACK = 1 << LINE_OK, 1 << LINE_BAD, 1 << LINE_FALLBACK
@@ -129,6 +131,80 @@ class Where:
     def __repr__(self):
         return "Where(%r, %d, %r, hi=%r, kind=%s, group=%d, negate=%r)" % (self.path, self.op, self.value, self.hi,
                                                                             self.kind.__name__, self.group, self.negate)
+
+
+class LpGroupKey(ctypes.Structure):
+    """lp_group_key (include/logparser_amd.h)"""
+    _fields_ = [("path", ctypes.c_char_p), ("kind", ctypes.c_int32)]
+
+
+class LpGroupAgg(ctypes.Structure):
+    """lp_group_agg (include/logparser_amd.h)"""
+    _fields_ = [("path", ctypes.c_char_p), ("op", ctypes.c_int32), ("value", ctypes.c_void_p), ("valid", ctypes.c_void_p)]
+
+
+class LpGroupOut(ctypes.Structure):
+    """lp_group_out (include/logparser_amd.h)"""
+    _fields_ = [("rep", ctypes.c_void_p), ("group_of", ctypes.c_void_p), ("groups_cap", ctypes.c_int64),
+                ("n_groups", ctypes.c_int64)]
+
+
+# lp_result_group's aggregates (LP_AGG_*) and limits
+AGG_COUNT_ROWS, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = range(5)
+GROUP_MAX_KEYS, GROUP_MAX_AGGS = 4, 8
+# the device call's default LDS budget in 8-byte words (csrc/lp_group.h GROUP_LDS_WORDS)
+GROUP_LDS_WORDS = 4096
+
+
+class Agg:
+    """One aggregate of BatchResult.group_*: AGG_COUNT_ROWS (no path: the
+    group's rows), or AGG_COUNT / AGG_SUM / AGG_MIN / AGG_MAX of `path` (a
+    requested "TYPE:path", a wildcard's member, or a LONG pseudo-column) taken
+    as a BIGINT column: the rows on which it is not null, and the wrapping
+    sum, the least and the greatest of those values.  Argument errors raise
+    here, before any engine call."""
+
+    def __init__(self, op, path=None):
+        if isinstance(op, bool) or not isinstance(op, int) or op not in range(5):
+            raise ValueError("Agg: unknown op %r" % (op,))
+        if op == AGG_COUNT_ROWS:
+            if path is not None:
+                raise ValueError("Agg: AGG_COUNT_ROWS takes no path")
+        elif not isinstance(path, str) or not path:
+            raise ValueError("Agg: path must be a non-empty str")
+        self.op, self.path = op, path
+
+    def __repr__(self):
+        return "Agg(%d, %r)" % (self.op, self.path)
+
+
+def group_acc_words(aggs):
+    """accumulator words per group of a list of Agg (csrc/lp_group.h): the
+    rows, one non-null count per distinct measure, one per SUM / MIN / MAX"""
+    return 1 + len({a.path for a in aggs if a.path is not None}) + sum(1 for a in aggs if a.op >= AGG_SUM)
+
+
+def _group_args(keys, aggs):
+    """(lp_group_key array or None, lp_group_agg array or None) of [(path, str | int)] and a list of Agg"""
+    keys, aggs = list(keys), list(aggs)
+    if len(keys) > GROUP_MAX_KEYS:
+        raise ValueError("at most %d keys" % GROUP_MAX_KEYS)
+    if len(aggs) > GROUP_MAX_AGGS:
+        raise ValueError("at most %d aggregates" % GROUP_MAX_AGGS)
+    if any(not isinstance(a, Agg) for a in aggs):
+        raise TypeError("aggs: Agg objects expected")
+    for k in keys:
+        if not (isinstance(k, tuple) and len(k) == 2 and isinstance(k[0], str) and k[0] and k[1] in (int, str)):
+            raise ValueError("keys: (path, str | int) pairs expected")
+    karr = (LpGroupKey * len(keys))() if keys else None
+    for j, (path, typ) in enumerate(keys):
+        karr[j].path = path.encode()
+        karr[j].kind = CAST_LONG if typ is int else CAST_STRING
+    aarr = (LpGroupAgg * len(aggs))() if aggs else None
+    for j, a in enumerate(aggs):
+        aarr[j].path = a.path.encode() if a.path is not None else None
+        aarr[j].op = a.op
+    return karr, aarr
 
 
 def _where_array(terms):
@@ -303,6 +379,9 @@ _DICT_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are deri
 _ARROW_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a column's values are derived on the host only: use to_arrow"),
                  LP_E_MISSING: (MissingDissectorsException, "lp_result_arrow: a path the parser does not deliver"),
                  None: (ValueError, "lp_result_arrow failed: %d")}
+_GROUP_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a key's or measure's values are derived on the host only: use group_from"),
+                 LP_E_MISSING: (MissingDissectorsException, "lp_result_group: a path the parser does not deliver"),
+                 None: (ValueError, "lp_result_group failed: %d")}
 _MAP_ERRORS = {LP_E_UNSUPPORTED: (FallbackRequired, "a map column's members are derived on the host only: use table_map_from"),
                LP_E_MISSING: (MissingDissectorsException, "lp_result_table_map: a path the parser does not deliver"),
                None: (ValueError, "lp_result_table_map failed: %d")}
@@ -412,6 +491,14 @@ def lib():
     L.lp_result_table_dict_rows.restype = ctypes.c_int
     L.lp_result_table_dict_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
                                             ctypes.POINTER(LpTableDictCol), ctypes.c_int, ctypes.c_int]
+    L.lp_result_group.restype = ctypes.c_int
+    L.lp_result_group.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_int64, ctypes.c_int64,
+                                  ctypes.POINTER(LpGroupKey), ctypes.c_int, ctypes.POINTER(LpGroupAgg), ctypes.c_int,
+                                  ctypes.POINTER(LpGroupOut), ctypes.c_int]
+    L.lp_result_group_rows.restype = ctypes.c_int
+    L.lp_result_group_rows.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(LpGroupKey), ctypes.c_int, ctypes.POINTER(LpGroupAgg), ctypes.c_int,
+                                       ctypes.POINTER(LpGroupOut), ctypes.c_int]
     L.lp_result_arrow.restype = ctypes.c_int
     L.lp_result_arrow.argtypes = [ctypes.c_void_p, ctypes.POINTER(LpResult), ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_int64, ctypes.POINTER(LpArrowCol), ctypes.c_int, ctypes.c_int,
@@ -1077,6 +1164,75 @@ class BatchResult:
         {"values": k_table_values of the rows, "insert": table reset + k_dict_insert,
         "index": k_dict_mark + rank scan + k_dict_index, "dict": the dictionary's values}"""
         return dict(zip(("values", "insert", "index", "dict"), self._timing(12, 16)))
+
+    def _group(self, res, keys, aggs, first, count, rows_p, threads, alloc, ptr, groups_cap):
+        """lp_result_group / _rows with the size protocol: a call that counts
+        the groups (groups_cap: room allotted at once), one that fills"""
+        karr, aarr = _group_args(keys, aggs)
+        n_keys, n_aggs = len(karr) if karr else 0, len(aarr) if aarr else 0
+        L, h = lib(), self._p._h
+        out = LpGroupOut()
+        group_of = alloc(max(1, count), "int32")
+        out.group_of = ptr(group_of)
+        bufs = {}
+
+        def room(n):
+            bufs["rep"] = alloc(max(1, n), "int64")
+            bufs["aggs"] = [(alloc(max(1, n), "int64"), alloc(max(1, n), "uint8")) for _ in range(n_aggs)]
+            out.rep, out.groups_cap = ptr(bufs["rep"]), n
+            for j in range(n_aggs):
+                aarr[j].value, aarr[j].valid = ptr(bufs["aggs"][j][0]), ptr(bufs["aggs"][j][1])
+
+        room(groups_cap or 0)
+
+        def call():
+            if rows_p is None:
+                return L.lp_result_group(h, ctypes.byref(res), first, count, karr, n_keys, aarr, n_aggs, ctypes.byref(out),
+                                         threads)
+            return L.lp_result_group_rows(h, ctypes.byref(res), rows_p, count, karr, n_keys, aarr, n_aggs,
+                                          ctypes.byref(out), threads)
+        _sized_call(call, lambda: room(out.n_groups), _GROUP_ERRORS)
+        n = out.n_groups
+        return {"n_groups": n, "rep": bufs["rep"][:n], "group_of": group_of[:count],
+                "aggs": [(v[:n], ok[:n]) for v, ok in bufs["aggs"]]}
+
+    def group_device(self, keys, aggs, first=0, count=None, rows=None, groups_cap=None):
+        """lp_result_group on the device view: GROUP BY keys over rows [first,
+        first+count) -- or, with rows (a torch int64 tensor on the device, as
+        select_where_device returns; not together with first / count), over
+        exactly those lines.  keys: [(path, str | int)] (at most 4; int: equal
+        by value, str: by bytes; null is a key value of its own); aggs: a
+        list of Agg (at most 8).  Returns {"n_groups", "rep": int64
+        [n_groups] each group's first line, "group_of": int32 [count] every
+        row's group, "aggs": [(value int64 [n_groups], valid uint8
+        [n_groups])]} of torch tensors on the handle's device; groups in the
+        order of first occurrence; table_device(keys, rows=rep) gives their
+        key values.  No key or measure column is built.  groups_cap: room
+        allotted at once (default: the call is repeated once the groups are
+        counted)."""
+        import torch
+        rows_p, first, count = self._window(rows, first, count, True)
+        dev = torch.device("cuda", self._p.device)
+        dt = {"int64": torch.int64, "int32": torch.int32, "uint8": torch.uint8}
+        return self._group(self._view(), keys, aggs, first, count, rows_p, 0,
+                           lambda n, t: torch.empty(n, dtype=dt[t], device=dev), lambda a: a.data_ptr(), groups_cap)
+
+    def group_from(self, res, keys, aggs, first=0, count=None, rows=None, threads=16, decode=True):
+        """lp_result_group from a host copy (with the input): the same arrays
+        as group_device, as numpy arrays (bit-identical to the device's).
+        decode: also "keys": {path: (values, valid)}, the groups' key values
+        as table_from(rows=rep) gives them."""
+        rows_p, first, count = self._window(rows, first, count, False)
+        out = self._group(res, keys, aggs, first, count, rows_p, threads, lambda n, t: np.zeros(n, dtype=t),
+                          lambda a: a.ctypes.data, None)
+        if decode:
+            out["keys"] = self.table_from(res, list(keys), rows=np.ascontiguousarray(out["rep"]), threads=threads) if keys else {}
+        return out
+
+    def group_timing(self):
+        """HIP-event ms of the last device lp_result_group's phases: {"insert": resets + k_group_insert,
+        "index": k_dict_mark + rank scan + k_dict_index, "aggregate": fill + k_group_agg + k_group_finish}"""
+        return dict(zip(("insert", "index", "aggregate"), self._timing(20, 23)))
 
     def _map_call(self, res, paths, first, count, threads, alloc, bufs, rows_p=None):
         """lp_result_table_map with lp_result_table's size protocol: a first

@@ -128,7 +128,7 @@ bool read_back(hipStream_t s, V* dst, const void* src) {
 }
 
 // where each family's phases start in lp_handle::tms (lp_last_timing index - 5)
-enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7, TMS_ARROW = 11, TMS_WHERE = 12 };
+enum { TMS_TABLE = 0, TMS_MAP = 3, TMS_SELECT = 6, TMS_DICT = 7, TMS_ARROW = 11, TMS_WHERE = 12, TMS_GROUP = 14 };
 
 }  // namespace
 
@@ -140,6 +140,7 @@ struct lp_handle {
     DevBuf input, chunk, line_off, cols, arena, meta, waves, args, route, ovf, hist;
     DevBuf cstate;  // chunked parse: look-back words, per-chunk counts, queued lines
     DevBuf targs, tscratch;  // device table (lp_result_table on a device view)
+    DevBuf gacc;             // lp_result_group's accumulator words (sized once the groups are counted)
     // the GeoIP stages' images on this handle's device (lp_geoip.h): a tree per database, a
     // field table and its byte pool per stage; uploaded at compile time, released by lp_free
     DevBuf geo_tree[lp::N_GEODB], geo_fields[lp::MAX_VAL], geo_pool[lp::MAX_VAL];
@@ -172,9 +173,11 @@ struct lp_handle {
     // bytes phases; the map columns' count / entries / fill phases, summed over the columns;
     // lp_result_select's passes and scan; the dictionary columns' four phases, summed over the columns;
     // [16] lp_result_arrow's packaging kernels; ([17]: geo_ms;) [18..19] lp_result_select_where's
-    // predicate kernel and compaction
-    float tms[14]{};
+    // predicate kernel and compaction; [20..22] lp_result_group's insert, numbering and aggregation
+    float tms[17]{};
     int dict_hash_bits = 0;  // LP_OPT_DICT_HASH_BITS (tests: 0 = the whole hash)
+    int group_lds_words = 0; // LP_OPT_GROUP_LDS_WORDS (0: lp_group.h GROUP_LDS_WORDS, -1: none)
+    int group_peel = 0;      // LP_OPT_GROUP_PEEL (0: lp_group.h GROUP_PEEL_ROUNDS, -1: none)
     bool have_events = false;
     uint64_t counters[4]{};
     uint32_t chunk_lines = 0;      // LP_OPT_CHUNK_LINES (0: the kernel's default)
@@ -783,7 +786,7 @@ void lp_free(lp_handle* h) {
     hipSetDevice(h->device);
     if (h->pending) hipStreamSynchronize(h->stream);
     for (auto* b : {&h->input, &h->chunk, &h->line_off, &h->cols, &h->arena, &h->meta, &h->waves, &h->args, &h->route,
-                    &h->ovf, &h->hist, &h->cstate, &h->targs, &h->tscratch})
+                    &h->ovf, &h->hist, &h->cstate, &h->targs, &h->tscratch, &h->gacc})
         b->release();
     for (auto& b : h->geo_tree) b.release();
     for (auto& b : h->geo_fields) b.release();
@@ -853,6 +856,14 @@ int lp_set_option(lp_handle* h, int option, int64_t value) {
     case LP_OPT_DICT_HASH_BITS:
         if (value < 0 || value > 32) return LP_E_INVALID;
         h->dict_hash_bits = (int)value;
+        return LP_OK;
+    case LP_OPT_GROUP_LDS_WORDS:
+        if (value < -1 || value > lp::GROUP_LDS_WORDS_MAX) return LP_E_INVALID;
+        h->group_lds_words = (int)value;
+        return LP_OK;
+    case LP_OPT_GROUP_PEEL:
+        if (value < -1 || value > lp::GROUP_PEEL_MAX) return LP_E_INVALID;
+        h->group_peel = (int)value;
         return LP_OK;
     default: return LP_E_INVALID;
     }
@@ -1028,7 +1039,9 @@ int lp_last_timing(lp_handle* h, float* out, int n) {
     if (n < 20) return 18;  // (a caller of the 18 values sees what it always saw)
     out[18] = h->tms[TMS_WHERE];
     out[19] = h->tms[TMS_WHERE + 1];
-    return 20;
+    if (n < 23) return 20;  // (a caller of the 20 values sees what it always saw)
+    for (int k = 0; k < 3; ++k) out[20 + k] = h->tms[TMS_GROUP + k];
+    return 23;
 }
 
 int lp_last_bytes(lp_handle* h, uint64_t* out, int n) {
@@ -2081,6 +2094,214 @@ int lp_result_select(lp_handle* h, const lp_result* r, int64_t first, int64_t co
 int lp_result_select_where(lp_handle* h, const lp_result* r, int64_t first, int64_t count, uint32_t status_mask,
                            const lp_where_term* terms, int n_terms, int64_t* rows, uint64_t rows_cap, uint64_t* rows_len) {
     return select_any(h, r, first, count, status_mask, terms, n_terms, rows, rows_cap, rows_len);
+}
+
+// ---- grouped aggregates (GROUP BY): lp_result_group / lp_result_group_rows
+namespace {
+// the checked arguments of a call, in both modes: the distinct measure paths in the order of
+// their first aggregate, and the accumulator words (lp_group.h)
+struct GroupSpec {
+    std::vector<std::string> meas;
+    lp::GroupAccs A{};
+};
+}  // namespace
+
+static int check_group(lp_handle* h, int64_t count, const lp_group_key* keys, int n_keys, const lp_group_agg* aggs,
+                       int n_aggs, lp_group_out* out, GroupSpec& S) {
+    if (n_keys < 0 || n_keys > LP_GROUP_MAX_KEYS || (n_keys > 0 && !keys)) return LP_E_INVALID;
+    if (n_aggs < 0 || n_aggs > LP_GROUP_MAX_AGGS || (n_aggs > 0 && !aggs)) return LP_E_INVALID;
+    if (out->groups_cap < 0 || (out->groups_cap > 0 && !out->rep) || count > 0x7FFFFFFF) return LP_E_INVALID;
+    for (int c = 0; c < n_keys; ++c)
+        if (!keys[c].path || (keys[c].kind != LP_CAST_STRING && keys[c].kind != LP_CAST_LONG)) return LP_E_INVALID;
+    int32_t op[LP_GROUP_MAX_AGGS], meas[LP_GROUP_MAX_AGGS];
+    for (int a = 0; a < n_aggs; ++a) {
+        const lp_group_agg& G = aggs[a];
+        if (G.op < LP_AGG_COUNT_ROWS || G.op > LP_AGG_MAX || (G.op == LP_AGG_COUNT_ROWS) != (G.path == nullptr))
+            return LP_E_INVALID;
+        if (out->groups_cap > 0 && (!G.value || !G.valid)) return LP_E_INVALID;
+        op[a] = G.op;
+        meas[a] = -1;
+        if (!G.path) continue;
+        const auto it = std::find(S.meas.begin(), S.meas.end(), G.path);
+        meas[a] = (int32_t)(it - S.meas.begin());
+        if (it == S.meas.end()) S.meas.push_back(G.path);
+    }
+    for (int c = 0; c < n_keys; ++c)
+        if (const int st = check_path(h, keys[c].path, keys[c].kind)) return st;
+    for (const std::string& p : S.meas)
+        if (const int st = check_path(h, p, LP_CAST_LONG)) return st;
+    S.A = lp::group_accs(n_aggs, op, meas, (int)S.meas.size());
+    return LP_OK;
+}
+
+// On a device view (group.hip; kernels.h GroupLayout): the keys' hash and the
+// insert, the dictionary's numbering, then -- the groups counted and found to
+// fit -- the accumulation.
+static int group_device(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                        const lp_group_key* keys, int n_keys, const lp_group_agg* aggs, int n_aggs, lp_group_out* out,
+                        const GroupSpec& S) {
+    if (ensure_synced(h) != LP_OK) return LP_E_STATE;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
+    if (out->groups_cap > 0) {  // every array the kernels write is memory of the device
+        if (!device_memory(h, out->rep)) return LP_E_INVALID;
+        for (int a = 0; a < n_aggs; ++a)
+            if (!device_memory(h, aggs[a].value) || !device_memory(h, aggs[a].valid)) return LP_E_INVALID;
+    }
+    if (count > 0 && out->group_of && !device_memory(h, out->group_of)) return LP_E_INVALID;
+    const int n_meas = (int)S.meas.size();
+    auto ta = table_args(h, first, count, rows, n_keys + n_meas);
+    std::string names;
+    for (int c = 0; c < n_keys + n_meas; ++c) {
+        lp::TableCol& T = ta->cols[c];
+        const std::string path = c < n_keys ? keys[c].path : S.meas[(size_t)(c - n_keys)];
+        T.kind = c < n_keys ? keys[c].kind : LP_CAST_LONG;
+        if (!h->plan.table_src(path, T.src, names, T.alt))  // (false also when the names pool is full)
+            return names.size() + path.size() > (size_t)lp::TABLE_NAMES ? LP_E_INVALID : LP_E_UNSUPPORTED;
+    }
+    memcpy(ta->names, names.data(), names.size());
+    if (count == 0) return LP_OK;  // (no launch, no event: lp_last_timing [20..22] keep the last call's)
+    hipSetDevice(h->device);
+    hipStream_t s = h->stream;
+    if (!h->targs.ensure(sizeof(lp::TableArgs))) return LP_E_NOMEM;
+    const lp::GroupLayout L = lp::group_layout(count);
+    if (!h->tscratch.ensure(L.total)) return LP_E_NOMEM;
+    lp::GroupArgs ga{};
+    lp::DictArgs da{};
+    ga.count = da.count = count;
+    ga.n_keys = n_keys;
+    ga.hash_bits = h->dict_hash_bits;
+    ga.peel = h->group_peel < 0 ? 0 : h->group_peel == 0 ? lp::GROUP_PEEL_ROUNDS : h->group_peel;
+    ga.A = S.A;
+    lp::group_bind(ga, da, *ta, L, h->tscratch.p, out->group_of);
+    if (hipMemcpyAsync(h->targs.p, ta.get(), sizeof(lp::TableArgs), hipMemcpyHostToDevice, s) != hipSuccess) return LP_E_DEVICE;
+    const lp::DeviceArgs* d_args = h->args.as<lp::DeviceArgs>();
+    const lp::TableArgs* d_targs = h->targs.as<lp::TableArgs>();
+    PhaseTimer T{h->tev, s};  // start, insert done, numbering done, aggregation done
+    T.mark(0);
+    if (lp::launch_group_insert(d_args, d_targs, *ta, ga, h->d_buf, s) != 0) return LP_E_DEVICE;
+    T.mark(1);
+    const uint32_t* d_total = nullptr;
+    if (lp::launch_dict_rank(da, L.d, h->tscratch.p, s, &d_total) != 0 || lp::launch_dict_index(*ta, da, s) != 0)
+        return LP_E_DEVICE;
+    T.mark(2);
+    uint32_t total = 0, fail = 0, bad_row = 0;
+    if (!read_back(s, &total, d_total) || !read_back(s, &fail, da.fail) || !read_back(s, &bad_row, ta->bad_row))
+        return LP_E_DEVICE;
+    if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+    if (bad_row) return LP_E_INVALID;  // a rows[k] outside the batch
+    if (fail) return LP_E_DEVICE;      // a probe ran out of slots
+    out->n_groups = (int64_t)total;
+    if (out->n_groups > out->groups_cap) return LP_E_NOMEM;
+    if (!h->gacc.ensure(8 * (size_t)total * (size_t)S.A.n_words)) return LP_E_NOMEM;
+    ga.n_groups = out->n_groups;
+    ga.acc = h->gacc.as<int64_t>();
+    if (hipMemcpyAsync(out->rep, (const void*)da.reps, 8 * (size_t)total, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return LP_E_DEVICE;
+    const int64_t budget = h->group_lds_words < 0 ? 0 : h->group_lds_words == 0 ? lp::GROUP_LDS_WORDS : h->group_lds_words;
+    if (lp::launch_group_agg(d_args, d_targs, *ta, ga, h->d_buf, budget, s, nullptr) != 0) return LP_E_DEVICE;
+    lp::GroupOut go{};
+    go.groups = out->n_groups;
+    for (int a = 0; a < n_aggs; ++a) {
+        go.value[a] = aggs[a].value;
+        go.valid[a] = aggs[a].valid;
+    }
+    if (lp::launch_group_finish(ga, go, s) != 0) return LP_E_DEVICE;
+    T.mark(3);
+    if (hipStreamSynchronize(s) != hipSuccess) return LP_E_DEVICE;
+    for (int k = 0; k < 3; ++k) h->tms[TMS_GROUP + k] = T.elapsed(k, k + 1);
+    return LP_OK;
+}
+
+// rows null: row k = line first + k
+static int group_any(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const int64_t* rows,
+                     const lp_group_key* keys, int n_keys, const lp_group_agg* aggs, int n_aggs, lp_group_out* out,
+                     int threads) {
+    if (!h || !r || !out) return LP_E_INVALID;
+    out->n_groups = 0;
+    GroupSpec S;
+    if (const int st = check_group(h, count, keys, n_keys, aggs, n_aggs, out, S)) return st;
+    if (!r->on_host)
+        return view_current(h, r) ? group_device(h, r, first, count, rows, keys, n_keys, aggs, n_aggs, out, S) : LP_E_STATE;
+    if (!r->input) return LP_E_INVALID;
+    if (const int st = check_rows(h, r, first, count, rows)) return st;
+    if (count == 0) return LP_OK;
+    // a host copy: the host table's columns of the keys and the distinct measures, then a hash map in row order
+    const int n_meas = (int)S.meas.size(), n_cols = n_keys + n_meas;
+    std::vector<lp_table_col> tc((size_t)n_cols);
+    std::vector<std::vector<uint8_t>> valid((size_t)n_cols, std::vector<uint8_t>((size_t)count, 0));
+    std::vector<std::vector<int64_t>> i64((size_t)n_cols, std::vector<int64_t>((size_t)count + 1, 0));
+    std::vector<std::vector<char>> chars((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) {
+        tc[c] = lp_table_col{};
+        tc[c].path = c < n_keys ? keys[c].path : S.meas[(size_t)(c - n_keys)].c_str();
+        tc[c].kind = c < n_keys ? keys[c].kind : LP_CAST_LONG;
+        tc[c].valid = valid[c].data();
+        tc[c].i64 = i64[c].data();
+    }
+    if (n_cols > 0) {
+        int st = table_any(h, r, first, count, rows, tc.data(), n_cols, threads);
+        if (st == LP_E_NOMEM) {
+            for (int c = 0; c < n_cols; ++c) {
+                chars[c].resize((size_t)tc[c].chars_len + 1);
+                tc[c].chars = chars[c].data();
+                tc[c].chars_cap = tc[c].chars_len;
+            }
+            st = table_any(h, r, first, count, rows, tc.data(), n_cols, threads);
+        }
+        if (st != LP_OK) return st;
+    }
+    const lp::GroupAccs& A = S.A;
+    const int W = A.n_words;
+    std::unordered_map<std::string, int32_t> seen;
+    std::vector<int64_t> reps, acc;
+    std::vector<int32_t> group_of((size_t)count, 0);
+    std::string key;
+    for (int64_t k = 0; k < count; ++k) {
+        key.clear();  // per key: a null tag, then the int64 or the length and the bytes
+        for (int c = 0; c < n_keys; ++c) {
+            key.push_back(valid[c][(size_t)k] ? 1 : 0);
+            if (!valid[c][(size_t)k]) continue;
+            if (keys[c].kind == LP_CAST_LONG) {
+                key.append((const char*)&i64[c][(size_t)k], 8);
+            } else {
+                const int64_t n = i64[c][(size_t)k + 1] - i64[c][(size_t)k];
+                key.append((const char*)&n, 8);
+                if (n > 0) key.append(chars[c].data() + i64[c][(size_t)k], (size_t)n);
+            }
+        }
+        auto it = seen.find(key);
+        if (it == seen.end()) {
+            it = seen.emplace(key, (int32_t)reps.size()).first;
+            reps.push_back(rows ? rows[k] : first + k);
+            for (int w = 0; w < W; ++w) acc.push_back(lp::group_identity(A.wkind[w]));
+        }
+        const int32_t g = it->second;
+        group_of[(size_t)k] = g;
+        int64_t* w = acc.data() + (size_t)g * (size_t)W;
+        for (int x = 0; x < W; ++x) {
+            const int m = A.wmeas[x];
+            const bool ok = m >= 0 && valid[n_keys + m][(size_t)k];
+            w[x] = lp::group_merge(A.wkind[x], w[x], lp::group_contrib(A.wkind[x], ok, ok ? i64[n_keys + m][(size_t)k] : 0));
+        }
+    }
+    out->n_groups = (int64_t)reps.size();
+    if (out->n_groups > out->groups_cap) return LP_E_NOMEM;  // (nothing written)
+    memcpy(out->rep, reps.data(), 8 * reps.size());
+    if (out->group_of) memcpy(out->group_of, group_of.data(), 4 * (size_t)count);
+    for (int64_t g = 0; g < out->n_groups; ++g)
+        for (int a = 0; a < n_aggs; ++a)
+            aggs[a].value[g] = lp::group_value(A, a, acc.data() + (size_t)g * (size_t)W, aggs[a].valid[g]);
+    return LP_OK;
+}
+
+int lp_result_group(lp_handle* h, const lp_result* r, int64_t first, int64_t count, const lp_group_key* keys, int n_keys,
+                    const lp_group_agg* aggs, int n_aggs, lp_group_out* out, int threads) {
+    return group_any(h, r, first, count, nullptr, keys, n_keys, aggs, n_aggs, out, threads);
+}
+
+int lp_result_group_rows(lp_handle* h, const lp_result* r, const int64_t* rows, int64_t n_rows, const lp_group_key* keys,
+                         int n_keys, const lp_group_agg* aggs, int n_aggs, lp_group_out* out, int threads) {
+    return rows_arg(rows, n_rows) ? group_any(h, r, 0, n_rows, rows, keys, n_keys, aggs, n_aggs, out, threads) : LP_E_INVALID;
 }
 
 // ---- Arrow C Data Interface export (arrow_export.cpp, lp_arrow.h)

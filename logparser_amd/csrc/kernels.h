@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lp_group.h"
 #include "lp_program.h"
 #include "lp_table.h"
 
@@ -192,6 +193,64 @@ int launch_select_write(const uint8_t* status, int64_t first, int64_t count, uin
 // one bit per line into wa.bits
 int launch_where_eval(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const uint8_t* buf,
                       const WhereArgs& wa, hipStream_t s);
+
+// lp_result_group on a device view (group.hip, lp_group.h): GroupArgs.  The rows are
+// a TableArgs' (first / count or rows, n_lines, bad_row); its columns without
+// output pointers are the n_keys keys (kind 1 STRING / 2 LONG), then the
+// distinct measures (LONG).  Scratch: hash [count] each row's key hash, valid
+// [count] 1 for a row inside the batch, and the dictionary's slots [cap] /
+// slot / flag / rank / reps (lp_table.h DictArgs, bound to the same arrays:
+// k_dict_mark, the rank scan and k_dict_index number the groups).  acc:
+// n_groups x A.n_words accumulator words, group-major.
+struct GroupArgs {
+    int64_t count;
+    int32_t n_keys, hash_bits;  // hash_bits: LP_OPT_DICT_HASH_BITS
+    uint32_t cap;
+    int32_t peel;               // the direct regime's peel rounds (0: none)
+    LP_G uint64_t* hash;
+    LP_G uint8_t* valid;
+    LP_G uint32_t *slots, *slot;
+    LP_G uint32_t* fail;        // set when a probe ran out
+    const LP_G int32_t* group_of;
+    LP_G int64_t* acc;
+    int64_t n_groups;
+    GroupAccs A;
+};
+// the caller's arrays of the aggregates (k_group_finish)
+struct GroupOut {
+    int64_t groups;  // min(n_groups, groups_cap)
+    LP_G int64_t* value[GROUP_MAX_AGGS];
+    LP_G uint8_t* valid[GROUP_MAX_AGGS];
+};
+// The call's launches (group.hip).
+// GroupLayout: the byte offsets of the call's scratch arrays for count rows,
+// beside DictLayout -- the slot table (2 count + 1 words: 8 bytes per row), hash
+// 8, slot 4, flag 4, rank 4, reps 8, valid 1, group_of 4 (used when the caller
+// passes none): 41 bytes per row, plus the rank scan's temporaries; d.tmp /
+// d.tmp_bytes are what launch_dict_rank reads.  The accumulators are not part
+// of it: their size is known only once the groups are counted.
+//   launch_group_insert  the table reset, then one lane per row: the key
+//                        tuple's hash, stored, and lp_dict.h's insert
+//   (launch_dict_rank / launch_dict_index on the DictArgs group_bind fills:
+//   the groups' first rows, their numbers, group_of and the representatives)
+//   launch_group_agg     (ga.n_groups, ga.acc, ga.group_of set) the words'
+//                        identities, then one lane per row: privatised in LDS
+//                        when n_groups x words <= lds_words, else direct with
+//                        ga.peel peel rounds; *privatised: which one ran
+//   launch_group_finish  value / valid of go.groups groups out of the words
+struct GroupLayout {
+    size_t slots, hash, slot, flag, rank, reps, valid, group_of, words, total;
+    DictLayout d;
+    uint32_t cap;
+};
+GroupLayout group_layout(int64_t count);
+// binds ga's and da's scratch pointers (da.index: the caller's group_of, or the scratch's) and ta.bad_row
+void group_bind(GroupArgs& ga, DictArgs& da, TableArgs& ta, const GroupLayout& L, void* scratch, int32_t* group_of);
+int launch_group_insert(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const GroupArgs& ga,
+                        const uint8_t* buf, hipStream_t s);
+int launch_group_agg(const DeviceArgs* d_args, const TableArgs* d_targs, const TableArgs& ta, const GroupArgs& ga,
+                     const uint8_t* buf, int64_t lds_words, hipStream_t s, bool* privatised);
+int launch_group_finish(const GroupArgs& ga, const GroupOut& go, hipStream_t s);
 
 // The Arrow export's packaging on device memory (arrow.hip).
 //   launch_arrow_validity  n_cols columns' valid bytes [n_rows] (n_rows > 0; any
