@@ -197,7 +197,9 @@ int64_t lp_possible_paths_dissectors(const char *logformats, int max_depth, cons
                                   and parse passes, is LP_E_INVALID */
 #define LP_OPT_FIXED_SHAPE 7   /* 1 (default): a handle whose compiled program equals one of the fixed
                                   shapes (common, combined with every path requested) is parsed by
-                                  that shape's instance of the chunk kernel, lp_counters out[11];
+                                  that shape's instance of the chunk kernel, lp_counters out[11]
+                                  (out[12]: lines of the batch whose first leaf that instance
+                                  matched with the element walk, not the straight-line one);
                                   0: by the instances per program class, as every other program */
 #define LP_OPT_DICT_HASH_BITS 8 /* tests: lp_result_table_dict on a device view keeps only this many low
                                   bits of a value's hash for its home slot (1..32; 0 = default, all 64

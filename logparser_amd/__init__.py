@@ -772,11 +772,12 @@ class BatchResult:
             if rc != LP_OK:
                 raise EngineUnavailable("lp_line_status failed: %d" % rc)
         self.status = st[: self.n_lines]
-        c = (ctypes.c_uint64 * 12)()
-        L.lp_counters(parser._h, c, 12)
+        c = (ctypes.c_uint64 * 13)()
+        L.lp_counters(parser._h, c, 13)
         self.counters = {"lines": c[0], "ok": c[1], "bad": c[2], "fallback": c[3]}
         self.diag = {"overflow_waves": c[4], "retries": c[5], "arena_ovf": c[6], "uri_overflow_waves": c[7],
-                     "deferred_chunks": c[8], "dfs_lines": c[9], "uri_repair_lines": c[10], "fixed_shape": c[11]}
+                     "deferred_chunks": c[8], "dfs_lines": c[9], "uri_repair_lines": c[10], "fixed_shape": c[11],
+                     "walk_lines": c[12]}
         t = (ctypes.c_float * 3)()
         L.lp_last_timing(parser._h, t, 3)
         self.timing_ms = {"total": t[0], "index": t[1], "parse": t[2]}
@@ -1572,15 +1573,15 @@ class HttpdLoglineParser:
         rc = L.lp_sync(self._h)
         if rc != LP_OK:
             raise EngineUnavailable("lp_sync failed: %d" % rc)
-        c = (ctypes.c_uint64 * 12)()
-        L.lp_counters(self._h, c, 12)
+        c = (ctypes.c_uint64 * 13)()
+        L.lp_counters(self._h, c, 13)
         t = (ctypes.c_float * 5)()
         L.lp_last_timing(self._h, t, 5)
         b = (ctypes.c_uint64 * 4)()
         L.lp_last_bytes(self._h, b, 4)
         return {"lines": c[0], "ok": c[1], "bad": c[2], "fallback": c[3], "overflow_waves": c[4], "retries": c[5],
                 "arena_ovf": c[6], "uri_overflow_waves": c[7], "deferred_chunks": c[8], "dfs_lines": c[9],
-                "uri_repair_lines": c[10], "fixed_shape": c[11],
+                "uri_repair_lines": c[10], "fixed_shape": c[11], "walk_lines": c[12],
                 "ms_total": t[0], "ms_index": t[1], "ms_parse": t[2], "ms_parse_kernels": t[3], "ms_uri_kernels": t[4],
                 "bytes_in": b[0], "bytes_out": b[1], "bytes_parse_kernels": b[2], "bytes_uri_kernels": b[3]}
 

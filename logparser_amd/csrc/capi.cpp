@@ -187,6 +187,7 @@ struct lp_handle {
     uint64_t uri_ovf_waves = 0;    // waves of the last batch whose URI stages ran in k_uri_overflow
     uint64_t deferred = 0;         // chunks of the last batch parsed by the deferred pass (normally 0)
     uint64_t dfs_lines = 0;        // lines of the last batch the chunk kernel queued for the backtracking DFS
+    uint64_t walk_lines = 0;       // lines of the last batch whose first leaf took the element walk in a fixed-shape instance
     uint64_t uri_fix_lines = 0;    // lines of the last batch whose URI stages were redone with the repair on (uri_redo_line)
     uint64_t shard_top[LP_ARENA_SHARDS]{};
     lp::ParseLaunch last_launch{};  // the last enqueue's launch parameters (diagnostics)
@@ -610,6 +611,7 @@ int finish(lp_handle* h) {
             h->uri_ovf_waves = m.uri_ovf_waves;
             h->deferred = m.deferred;
             h->dfs_lines = m.dfs_lines;
+            h->walk_lines = m.walk_lines;
             h->uri_fix_lines = (m.uri_fix_lines & 0xFFFFFFFFull) + (m.uri_fix_lines >> 32);  // the queued ones, k_uri_overflow's own
         } else {
             h->counters[0] = (uint64_t)n;
@@ -994,11 +996,11 @@ int lp_counters(lp_handle* h, uint64_t* out, int n) {
     if (!h || !out) return LP_E_INVALID;
     const int st = ensure_synced(h);
     if (st != LP_OK) return st;
-    const uint64_t v[12] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_lines,
+    const uint64_t v[13] = {h->counters[0], h->counters[1], h->counters[2], h->counters[3], h->ovf_lines,
                             (uint64_t)h->retries, h->arena_ovf, h->uri_ovf_waves, h->deferred, h->dfs_lines,
-                            h->uri_fix_lines, (uint64_t)h->last_launch.shape};
-    for (int k = 0; k < n && k < 12; ++k) out[k] = v[k];
-    return n < 12 ? n : 12;
+                            h->uri_fix_lines, (uint64_t)h->last_launch.shape, h->walk_lines};
+    for (int k = 0; k < n && k < 13; ++k) out[k] = v[k];
+    return n < 13 ? n : 13;
 }
 
 int lp_histograms(lp_handle* h, uint64_t* out, int out_on_device) {

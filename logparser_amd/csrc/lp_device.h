@@ -1472,8 +1472,207 @@ __host__ __device__ LP_INLINE bool match_fixed_leaf_(const Program& P, const LN&
     (fixed_leaf_step<SHAPE, LA, (int)I>(P, L, caps, pos, ok), ...);
     return ok && pos == L.n;
 }
+// ---- the straight-line first leaf of the fixed shapes (lines with planes).
+// The element walk above asks the planes one question at a time, each a
+// lane-divergent loop with a dependent LDS read per step.  For the two fixed
+// shapes every question is about a handful of positions that the planes give
+// directly: the first three \s bits of the line (%h %l %u), the last quote
+// bits of the line (the greedy %r and the quoted fields after it), and the
+// first \s bit after the request's closing quote (%>s).  fixed_fast_leaf
+// reads the plane words that can hold them in one batch into registers with
+// static indices (head words from the line's first byte, tail words up to its
+// last byte), takes the positions with straight-line bit arithmetic, and
+// verifies from the bytes everything the walk would verify.
+//
+// It only accepts: true means the element walk (match_fixed_leaf_) succeeds
+// with exactly the spans written to caps; each condition stands next to the
+// element it replaces.  In every other case (a position outside the words, a
+// check that fails, too few quotes) it returns false having written nothing,
+// and the caller runs the unchanged walk, which alone decides BAD / REDO.
+namespace ff {
+constexpr int HEAD_WORDS = 2;  // %h %l %u and their separators lie in the line's first 128 bytes
+constexpr int TAIL_WORDS = 6;  // the last five quotes (combined) / the last one (common) in its last 384
+constexpr int NUM_BYTES = 12;  // digits of a CLFNUMBER token the SWAR test covers
+constexpr int STATUS_BYTES = 64;  // the ' ' that ends %>s lies in the one \s word read from the token's start
+// 64 bits from bit sh (0..63) of hi:lo
+__host__ __device__ LP_INLINE uint64_t funnel(uint64_t lo, uint64_t hi, int sh) {
+    return (lo >> sh) | ((hi << 1) << (63 - sh));
+}
+// bits [0, x) of a word, any x
+__host__ __device__ LP_INLINE uint64_t below(int x) { return x <= 0 ? 0ull : x >= 64 ? ~0ull : (1ull << x) - 1ull; }
+// EK_CLFNUMBER on exactly [a, b), 0 < b - a <= NUM_BYTES, b <= n: digits only, or "-"
+// (cand_first: the digit run from a ends at b when the byte at b is no
+// digit, which the caller has proved: a separator or the end of the line)
+template <typename LN>
+__host__ __device__ LP_INLINE bool clfnum_is(const LN& L, int a, int b) {
+    const uint32_t A = L.o + (uint32_t)a, W = A >> 2, s = A & 3;
+    const int len = b - a;
+    uint32_t w[4], v[3];
+    w[0] = L.word(W);
+    LP_UNROLL for (int j = 1; j < 4; ++j) w[j] = L.word_or0(W + j);
+    uint32_t nd = 0;
+    LP_UNROLL for (int j = 0; j < 3; ++j) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        v[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], s);
+#else
+        v[j] = (uint32_t)((((uint64_t)w[j + 1] << 32) | w[j]) >> (8 * s));
+#endif
+        nd |= ~swar::digit(v[j]) & swar::HI & (uint32_t)below(8 * (len - 4 * j));
+    }
+    return nd == 0 || (len == 1 && (v[0] & 0xFFu) == '-');
+}
+// the first len (<= 4) bytes at p (p < n) against a literal's lit4
+template <typename LN>
+__host__ __device__ LP_INLINE bool bytes_are(const LN& L, int p, uint32_t lit4, int len) {
+    return ((load_u32_at(L, p) ^ lit4) & (uint32_t)below(8 * len)) == 0;
+}
+}  // namespace ff
+
+template <int SHAPE, typename LN, typename Caps>
+__host__ __device__ LP_INLINE bool fixed_fast_leaf(const LN& L, Caps& caps) {
+    static_assert(SHAPE == FS_COMBINED || SHAPE == FS_COMMON, "the shapes this walk was written for");
+    constexpr FixedShape S = fixed_shape(SHAPE);
+    // the element table stays the statement of the format: this walk is for
+    // %h %l %u %t "%r" %>s %b and then either the end or two quoted fields
+    static_assert(S.elems[0].kind == EK_NOSPACE && S.elems[1].lit4 == fs::lit4(" ") &&
+                  S.elems[2].kind == EK_CLFNUMBER && S.elems[3].lit4 == fs::lit4(" ") &&
+                  S.elems[4].kind == EK_NOSPACE && S.elems[5].lit4 == fs::lit4(" [") &&
+                  S.elems[6].kind == EK_TIME_US && S.elems[7].lit4 == fs::lit4("] \"") &&
+                  S.elems[8].kind == EK_ANY_GREEDY && S.elems[9].lit4 == fs::lit4("\" ") &&
+                  S.elems[10].kind == EK_NOSPACE && S.elems[11].lit4 == fs::lit4(" ") &&
+                  S.elems[12].kind == EK_CLFNUMBER, "lp_fixed.h drifted from fixed_fast_leaf");
+    constexpr bool QUOTED = SHAPE == FS_COMBINED;
+    if constexpr (QUOTED) {
+        static_assert(S.n_elems == 18 && S.elems[8].need == 5 && S.elems[13].lit4 == fs::lit4(" \"") &&
+                      S.elems[14].kind == EK_ANY_LAZY && S.elems[15].lit4 == fs::lit4("\" \"") &&
+                      S.elems[16].kind == EK_ANY_LAZY && S.elems[17].lit4 == fs::lit4("\""), "combined");
+    } else {
+        static_assert(S.n_elems == 13 && S.elems[8].need == 1 && S.elems[12].last, "common");
+    }
+    const int n = L.n;
+    if (n <= 0) return false;
+    // ---- the plane words, all reads before the first use
+    const int B0 = (int)(L.o >> 6), Bl = (int)((L.o + (uint32_t)n - 1) >> 6);  // the line's blocks
+    const uint32_t E = L.o + (uint32_t)n;                                        // (its terminator)
+    const int Eb = (int)(E >> 6);
+    uint64_t hb[ff::HEAD_WORDS + 1], tb[ff::TAIL_WORDS + 1];
+    LP_UNROLL for (int j = 0; j <= ff::HEAD_WORDS; ++j) hb[j] = L.mask(MC_WS, (uint32_t)(B0 + j < Bl ? B0 + j : Bl));
+    LP_UNROLL for (int j = 0; j <= ff::TAIL_WORDS; ++j) {
+        const int b = Eb - ff::TAIL_WORDS + j;
+        tb[j] = L.mask(MC_QUOTE, (uint32_t)(b < B0 ? B0 : b > Bl ? Bl : b));
+    }
+    // head word k: \s bit i = line byte 64 k + i; tail word k: QUOTE bit i =
+    // line byte n - 64 TAIL_WORDS + 64 k + i.  A block index clamped above
+    // only stands for bytes outside the line, whose bits are cleared here
+    // (head: >= n) or below (tail: < the request's start).
+    uint64_t H[ff::HEAD_WORDS], T[ff::TAIL_WORDS];
+    LP_UNROLL for (int k = 0; k < ff::HEAD_WORDS; ++k)
+        H[k] = ff::funnel(hb[k], hb[k + 1], (int)(L.o & 63)) & ff::below(n - 64 * k);
+    LP_UNROLL for (int k = 0; k < ff::TAIL_WORDS; ++k) T[k] = ff::funnel(tb[k], tb[k + 1], (int)(E & 63));
+    LP_PROF(48);
+    // ---- %h ' ' %l ' ' %u " [": EK_NOSPACE ends at the first \s (find_ws),
+    // so the three tokens end at the first three \s bits of the line
+    static_assert(ff::HEAD_WORDS == 2, "the three-bit extraction below is written for two words");
+    int sp[3];
+    bool ok = true;
+    LP_UNROLL for (int j = 0; j < 3; ++j) {
+        const bool lo = H[0] != 0;
+        ok = ok && (H[0] | H[1]) != 0;
+        sp[j] = lo ? ctz64(H[0]) : 64 + ctz64(H[1] | (1ull << 63));
+        H[0] = lo ? H[0] & (H[0] - 1) : H[0];
+        H[1] = lo ? H[1] : H[1] & (H[1] - 1);
+    }
+    const int s1 = sp[0], s2 = sp[1], s3 = sp[2];
+    const int t = s3 + 2;   // %t
+    const int p = t + 29;   // %r: after the 26 time bytes and `] "`
+    // (every byte read below lies in [0, n): positions are checked first)
+    if (!ok || p > n) return false;
+    // %l (EK_CLFNUMBER) is [s1 + 1, s2): not empty, digits or "-"
+    if (s2 - s1 - 1 < 1 || s2 - s1 - 1 > ff::NUM_BYTES) return false;
+    // the literals " ", " ", " [" (the \s plane also holds TAB) and `] "`
+    // (independent loads: '&', no branch between them)
+    ok = ((int)(L[s1] == ' ') & (int)(L[s2] == ' ') & (int)ff::bytes_are(L, s3, S.elems[5].lit4, 2) &
+          (int)ff::bytes_are(L, t + 26, S.elems[7].lit4, 3) & (int)ff::clfnum_is(L, s1 + 1, s2)) != 0;
+    // %t (EK_TIME_US): the same test (it reads [t, t + 26), t + 29 <= n)
+    ok = ok && time_us_ok(L, t);
+    if (!ok) return false;
+    // ---- the quotes of [p, n), from the end (the tail words' bits below p off)
+    const int base = n - 64 * ff::TAIL_WORDS;  // line position of tail bit 0
+    LP_UNROLL for (int k = 0; k < ff::TAIL_WORDS; ++k) T[k] &= ~ff::below(p - base - 64 * k);
+    // the last quote bit left in the tail words: its line position, -1 none
+    auto take_last = [&]() -> int {
+        int pos = -1;
+        bool done = false;
+        LP_UNROLL for (int k = ff::TAIL_WORDS - 1; k >= 0; --k) {
+            const bool here = !done && T[k] != 0;
+            const int b = msb64(T[k] | 1ull);
+            pos = here ? base + 64 * k + b : pos;
+            T[k] = here ? T[k] ^ (1ull << b) : T[k];
+            done = done || here;
+        }
+        return pos;
+    };
+    int a, z;  // %>s starts at a; %b ends at z
+    int Q5 = 0, Q4 = 0, Q3 = 0, Q2 = 0, Q1 = 0;
+    if constexpr (QUOTED) {
+        // %r (EK_ANY_GREEDY, need 5): kth_from_end gives the fifth quote of
+        // [p, n) from the end, Q5, and lit_last the last `" ` at or before it:
+        // Q5 itself when a ' ' follows.  A quote the walk meets after Q5 is
+        // the next of Q4 < Q3 < Q2 < Q1, as none lies between them.
+        Q1 = take_last(), Q2 = take_last(), Q3 = take_last(), Q4 = take_last(), Q5 = take_last();
+        if (Q5 < 0) return false;  // fewer than five in the words
+        // `"` ends the line (the last literal, then '$'); the user agent
+        // (EK_ANY_LAZY) from Q2 + 1 ends at the first quote after it: Q1
+        ok = Q1 == n - 1;
+        // the referer (EK_ANY_LAZY) from Q4 + 1 ends at the first `" "`, whose
+        // first candidate is Q3: it is there when ' ' and Q2 follow Q3
+        ok = ((int)ok & (int)(Q3 + 2 == Q2) & (int)(L[Q3 + 1] == ' ')) != 0;
+        a = Q5 + 2;
+        z = Q4 - 1;  // %b ' "': the quote that ends it is Q4
+        ok = ((int)ok & (int)(L[Q5 + 1] == ' ') & (int)(L[z] == ' ')) != 0;
+    } else {
+        // %r (EK_ANY_GREEDY, need 1): lit_last gives the last `" ` of [p, n):
+        // the last quote when a ' ' follows it
+        Q5 = take_last();
+        if (Q5 < 0 || Q5 + 2 >= n) return false;
+        ok = L[Q5 + 1] == ' ';
+        a = Q5 + 2;
+        z = n;  // %b (the last element) runs to the end of the line
+    }
+    // %>s (EK_NOSPACE) from a (< n) ends at the first \s, w1, which must be a
+    // ' ' (looked for in the STATUS_BYTES from a: one \s word, read where the
+    // line's own bytes put it); %b (EK_CLFNUMBER) is (w1, z): not empty,
+    // digits or "-"
+    static_assert(ff::STATUS_BYTES == 64, "one funnel-shifted word");
+    const uint32_t A = L.o + (uint32_t)a;
+    const int W = (int)(A >> 6);
+    const uint64_t ws = ff::funnel(L.mask(MC_WS, (uint32_t)W), L.mask(MC_WS, (uint32_t)(W < Bl ? W + 1 : Bl)), (int)(A & 63)) &
+                        ff::below(n - a);
+    const int w1 = a + ctz64(ws | (1ull << 63));
+    if (!ok || !ws || z - w1 - 1 < 1 || z - w1 - 1 > ff::NUM_BYTES) return false;
+    if (L[w1] != ' ' || !ff::clfnum_is(L, w1 + 1, z)) return false;
+    LP_PROF(49);
+    caps.set_u(S.elems[0].cap, mkspan(0, s1));
+    caps.set_u(S.elems[2].cap, mkspan(s1 + 1, s2));
+    caps.set_u(S.elems[4].cap, mkspan(s2 + 1, s3));
+    caps.set_u(S.elems[6].cap, mkspan(t, t + 26));
+    caps.set_u(S.elems[8].cap, mkspan(p, Q5));
+    caps.set_u(S.elems[10].cap, mkspan(a, w1));
+    caps.set_u(S.elems[12].cap, mkspan(w1 + 1, z));
+    if constexpr (QUOTED) {
+        caps.set_u(S.elems[14].cap, mkspan(Q4 + 1, Q3));
+        caps.set_u(S.elems[16].cap, mkspan(Q2 + 1, Q1));
+    }
+    return true;
+}
+
+// walked (optional): set when the line took the element walk
 template <int SHAPE, bool LA = true, typename LN, typename Caps>
-__host__ __device__ LP_INLINE bool match_fixed_leaf(const Program& P, const LN& L, Caps& caps) {
+__host__ __device__ LP_INLINE bool match_fixed_leaf(const Program& P, const LN& L, Caps& caps, bool* walked = nullptr) {
+    if constexpr (LN::has_masks) {
+        if (fixed_fast_leaf<SHAPE>(L, caps)) return true;
+    }
+    if (walked) *walked = true;
     return match_fixed_leaf_<SHAPE, LA>(P, L, caps, std::make_index_sequence<(size_t)fixed_shape(SHAPE).n_elems>{});
 }
 
@@ -2294,6 +2493,7 @@ struct LineOut {
     RegArr<MAX_SECMS> sm_lo, sm_hi;
     uint32_t bipdone;  // BinaryIP stage b delivered (bit b)
     RegArr<MAX_BINIP> bip;
+    uint32_t walked;   // a fixed-shape instance: the first leaf took the element walk (fixed_fast_leaf declined)
 };
 
 // A line's URI stages (the URI kernel): per query stage the piece table
@@ -2880,6 +3080,7 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
     o.tdone = 0;
     o.smdone = 0;
     o.bipdone = 0;
+    o.walked = 0;
     if constexpr (!PRE) o.caps.fill(0);
     o.fl_kind.fill(FL_NONE);
     o.fl_method.fill(0);
@@ -2910,7 +3111,9 @@ __host__ __device__ LP_INLINE void phase1(const Program& P, const EL& elems, con
         else o.caps.fill(0);  // the DFS sets its own
     } else {
         if constexpr (SHAPE != FS_NONE) {
-            if (match_fixed_leaf<SHAPE, LA>(P, L, o.caps)) st = ST_OK;
+            bool walked = false;
+            if (match_fixed_leaf<SHAPE, LA>(P, L, o.caps, &walked)) st = ST_OK;
+            o.walked = walked ? 1u : 0u;
         } else {
             if (P.n_fmt == 1 && match_first_leaf<LA, SIMPLE>(P, L, o.caps)) st = ST_OK;
         }

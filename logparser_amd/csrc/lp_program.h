@@ -404,7 +404,8 @@ struct Meta {
     // lines): how many failed, and the first failure (kind, then four values;
     // see check_fail in parse.hip).  Non-zero fails the batch (LP_E_DEVICE).
     unsigned long long err;
-    unsigned long long err_info[14];  // (13 used; with uri_fix_lines and dfs_lines it keeps shard_top on its own 128-B lines)
+    unsigned long long err_info[13];  // (with walk_lines, uri_fix_lines and dfs_lines it keeps shard_top on its own 128-B lines)
+    unsigned long long walk_lines;   // lines of a fixed-shape instance whose first leaf took the element walk (fixed_fast_leaf declined)
     unsigned long long uri_fix_lines;// lines whose URI needs uri_repair: low half, those k_uri_lines queued; high half, k_uri_overflow's own
     unsigned long long dfs_lines;    // lines the chunk kernel queued because the first leaf did not decide them (ST_REDO)
     unsigned long long shard_top[ARENA_SHARDS * 16];  // bump pointer of shard s at [16 s] (own 128-B line)

@@ -401,6 +401,7 @@ __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uin
     LineOut o;
     o.status = ST_OK;
     o.tdone = o.smdone = o.bipdone = 0;
+    o.walked = 0;
     LP_PROF(1);
     uint32_t mword = 0;  // MF: the line's match word (bit f: format f matches)
     if constexpr (MF) {
@@ -442,6 +443,10 @@ __device__ __forceinline__ void parse_chunk(const uint8_t* __restrict__ buf, uin
     {
         const uint32_t nredo = (uint32_t)__popcll(__ballot(mine && redo));
         if (nredo && lane == 0) atomicAdd(&C.meta->dfs_lines, (unsigned long long)nredo);
+    }
+    if constexpr (SHAPE != FS_NONE) {  // (diagnostic: no atomic for a chunk whose lines all took the straight-line leaf)
+        const uint32_t nwalk = (uint32_t)__popcll(__ballot(mine && lds_line && o.walked));
+        if (nwalk && lane == 0) atomicAdd(&C.meta->walk_lines, (unsigned long long)nwalk);
     }
     if (row) {
         write_line(P, o, C, li);

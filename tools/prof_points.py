@@ -41,7 +41,8 @@ names = {0: "start", 1: "staged", 2: "phase1 entry", 3: "guard", 4: "match", 5: 
          60: "chunk staged", 63: "DMA landed", 61: "line numbers", 62: "rows written",
          14: "strf parsed", 15: "strf resolved", 16: "strf fields", 27: "uri lane", 28: "uri gather loads",
          17: "q slots loaded", 18: "q prepared", 19: "q spill allocated",
-         29: "uri need", 20: "uri need scanned"}
+         29: "uri need", 20: "uri need scanned",
+         48: "fast leaf words", 49: "fast leaf accepted"}
 for u in range(2):
     for j, nm in enumerate(["pass1", "authority", "path", "query", "frag"]):
         names[30 + 8 * u + j] = "u%d %s done" % (u, nm)
@@ -50,7 +51,7 @@ for u in range(2):
     names[51 + 4 * u] = "u%d fast walk" % u
     names[52 + 4 * u] = "u%d gen walk" % u
 # the parse kernel, then the URI kernel (k_uri_lines): separate orders
-orders = [[0, 63, 60, 1, 2, 3, 4, 5, 14, 15, 16, 6, 7, 9, 61, 62],
+orders = [[0, 63, 60, 1, 2, 3, 48, 49, 4, 5, 14, 15, 16, 6, 7, 9, 61, 62],
           [23, 27, 28, 24, 25, 29, 20, 26, 10, 50, 51, 52, 30, 31, 32, 33, 34, 11, 12, 54, 55, 56, 38, 43, 44, 45, 46, 47, 39, 40, 41, 42, 13, 21, 17, 18, 19, 22]]
 print("parse ms %.3f  waves profiled %d  fixed shape %s" % (st["ms_parse"], int((T[:, 0] != 0).sum()), st.get("fixed_shape", "-")))
 for order in orders:
